@@ -9,14 +9,18 @@ compress every call, then decompress every call (the reference harness' "-D both
 `value` = uncompressed bytes moved in both directions by all ranks / max-over-ranks wall time (the reference
 counts uncompressed bytes for either direction and doubles them for "both", test/main.c:2336-2346).
 Multi-GPU: independent chunks shard across ranks with no data-path collective in the timed region (weak scaling:
-every rank owns its own buffer); gloo carries the barrier and the max/sum reductions of the timings.  After the timed
-region the ranks also build gzip-ext members the way BASELINE config 5 asks for - a striped volume: member m holds one
+every rank owns its own buffer); gloo carries the barrier and the max/sum reductions of the timings.  With --full, after the
+timed region the ranks also build gzip-ext members the way BASELINE config 5 asks for - a striped volume: member m holds one
 slice of every rank (--members, default 16 from 8 ranks on, else 4), the members are PIPELINED (while member m travels to
 rank 0's HBM the ranks compress member m + 1) - over peer-to-peer copies into an IPC window and over an RCCL send/recv
 group, both timed and both verified by decoding on rank 0: `config.one_stream`.  `python bench.py --gpus N` launches its own
 N ranks when no launcher set WORLD_SIZE.
 
-Beside the headline the line carries (rank 0, N = 1 only, all outside the timed region):
+A plain run sets up, warms up, times --steps steps and prints the line: the headline, the ratio, and the K1 / decode
+roofline figures that the timed steps' own HIP events give.  --dump-outputs DIR writes what the last timed step returned
+(dump_outputs below).  Everything else runs only with --full, after the timed region: the CRC check after the warm-up, the
+per-direction split (config.compress_GBps / decompress_GBps, per_rank), the lone K1 launch (roofline.full_launch_alone_ms),
+the one-stream leg (N > 1) and these parts of the line (rank 0, N = 1 only):
   config.api_*          the same work through qatzip.h itself: ONE qzCompress / qzDecompress call of --api-mb (2047) MiB on
                         qzMalloc(PINNED_MEM) buffers, PCIe both ways included, and its ratio to min(link, kernel rate)
                         (the decode takes the member in growing pieces while it arrives: profiles/r5_api_decompress_pieces.txt)
@@ -694,11 +698,37 @@ def one_stream_leg(ctx, qz, pg, rank, world, d_src, slice_mb, members, steps, nd
     return out
 
 
+def dump_outputs(path, ctx, d_comp, comp_len, dec_crc, d_back, back_n, block=CHUNK, blocks=32, seed=20250523):
+    """What the last timed step handed its caller, as .npy files in `path` (16 MiB or so): per call the compressed length,
+    the CRC-32 of the whole compressed stream (taken on the device) and the CRC-32 the decode returned, as float64; and, as
+    float32, `blocks` blocks of 64 KiB at seeded offsets of the compressed streams (spread over the calls) and of the last
+    call's decompressed output.  The offsets depend only on the seed and the lengths: two builds that compute the same
+    bytes dump the same files."""
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(seed)
+
+    def sample(buf, n, k):
+        b = min(block, n)
+        offs = np.sort(rng.integers(0, n - b + 1, k))
+        return np.concatenate([buf.download(b, int(o)) for o in offs]).astype(np.float32)
+    out = {"compressed_len": np.array(comp_len, np.float64),
+           "compressed_crc32": np.array([ctx.crc32(d, n) for d, n in zip(d_comp, comp_len)], np.float64),
+           "decompressed_crc32": np.array(dec_crc, np.float64),
+           "compressed_sample": np.concatenate([sample(d, n, max(1, blocks // len(d_comp))) for d, n in zip(d_comp, comp_len)]),
+           "decompressed_sample": sample(d_back, back_n, blocks)}
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2)
+    ap.add_argument("--steps", type=int, default=2, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true", help="also run what the headline does not need (see the module's doc): the CRC "
+                    "check, the per-direction split, the lone K1 launch, the extra legs, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy "
+                    "(rank 0; float32 / float64, about 16 MiB)")
     ap.add_argument("--mb", type=int, default=4096, help="buffer size per GPU in MiB (default: the 4 GB config)")
     ap.add_argument("--base-mb", type=int, default=128, help="distinct synthetic data generated per GPU (tiled)")
     ap.add_argument("--cpu-mb", type=int, default=64, help="CPU baseline: shard size per worker, MiB")
@@ -715,6 +745,8 @@ def main():
     ap.add_argument("--no-probe", action="store_true", help="skip the lone 12288-chunk K1 launch after the timed region "
                     "(the rocprofv3 --pmc passes: every K1 launch of the run is then a whole 2 GiB call)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.cpu_worker is not None:
         cpu_worker(args.cpu_worker, args.cpu_mb, args.cpu_data, args.cpu_pin)
         return
@@ -745,6 +777,7 @@ def main():
     d_back = ctx.alloc(max(call_n))
 
     comp_len = [0] * ncalls
+    dec_crc = [0] * ncalls
 
     def compress_all():
         for i, n in enumerate(call_n):
@@ -754,7 +787,7 @@ def main():
 
     def decompress_all():
         for i, n in enumerate(call_n):
-            iu, ol, crc = ctx.inflate_stream(d_comp[i], comp_len[i], d_back, CHUNK, want_crc=True)
+            iu, ol, dec_crc[i] = ctx.inflate_stream(d_comp[i], comp_len[i], d_back, CHUNK, want_crc=True)
             assert iu == comp_len[i] and ol == n
 
     def step():
@@ -763,8 +796,9 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    # parity guard outside the timed region: what came back is what went in
-    assert ctx.crc32(d_back, call_n[-1]) == ctx.crc32(view(qatzip_amd, d_src, (ncalls - 1) * CALL_BYTES, call_n[-1]), call_n[-1])
+    if args.full:
+        # parity guard outside the timed region: what came back is what went in
+        assert ctx.crc32(d_back, call_n[-1]) == ctx.crc32(view(qatzip_amd, d_src, (ncalls - 1) * CALL_BYTES, call_n[-1]), call_n[-1])
 
     ctx.k1_stats(reset=True)
     barrier(pg); ctx.sync()
@@ -776,26 +810,29 @@ def main():
     # dominant kernel (K1: the LZ77 parse, with K2 and the CRC in its waves): HIP events around every launch of the timed
     # region, on the stream it is launched on
     k1_ms, k1_launches, k1_chunks = ctx.k1_stats()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ctx, d_comp, comp_len, dec_crc, d_back, call_n[-1])
 
-    # per-direction split (untimed by the contract, reported alongside) and one K1 launch alone on the chip
-    ctx.sync(); t1 = time.perf_counter(); compress_all(); ctx.sync(); tc = time.perf_counter() - t1
-    t1 = time.perf_counter(); decompress_all(); ctx.sync(); td = time.perf_counter() - t1
-    inf_ms = ctx.inflate_timing()
-    batch_chunks = ctx.batch_chunks()         # three rounds over the resident waves: the probe launch below
-    probe_n = min(batch_chunks * CHUNK, call_n[0])
-    if not args.no_probe:
-        ctx.deflate_raw_async(view(qatzip_amd, d_src, 0, probe_n), probe_n, CHUNK, 1, 1, d_comp[0]); ctx.sync()
-    k_ms = ctx.timing()                      # the probe: one launch of three rounds over the resident waves
+    if args.full:
+        # per-direction split (untimed by the contract, reported alongside) and one K1 launch alone on the chip
+        ctx.sync(); t1 = time.perf_counter(); compress_all(); ctx.sync(); tc = time.perf_counter() - t1
+        t1 = time.perf_counter(); decompress_all(); ctx.sync(); td = time.perf_counter() - t1
+        batch_chunks = ctx.batch_chunks()         # three rounds over the resident waves: the probe launch below
+        probe_n = min(batch_chunks * CHUNK, call_n[0])
+        if not args.no_probe:
+            ctx.deflate_raw_async(view(qatzip_amd, d_src, 0, probe_n), probe_n, CHUNK, 1, 1, d_comp[0]); ctx.sync()
+        from qatzip_amd import shard as _shard
+        per_rank = _shard.allgather_floats(pg, [tc, td])                 # every rank's own compress / decompress pass (seconds)
+        tc = allreduce(pg, tc, "MAX"); td = allreduce(pg, td, "MAX")
+    inf_ms = ctx.inflate_timing()            # the last decode call's kernels
+    k_ms = ctx.timing()                      # the last compress call's (with --full: the probe, three rounds over the resident waves)
     comp_total = allreduce(pg, float(sum(comp_len)), "SUM")
     raw_total = float(total) * world
-    from qatzip_amd import shard as _shard
-    per_rank = _shard.allgather_floats(pg, [tc, td])                 # every rank's own compress / decompress pass (seconds)
-    tc = allreduce(pg, tc, "MAX"); td = allreduce(pg, td, "MAX")
 
     extra = {}
     one = None
     hard_exit = False
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         if world > 1:
             # The leg runs on a helper thread with a deadline: its transports wait for other ranks on the device (RCCL) or
             # in bounded polls (IPC window), and a rank that fell out of step must not take the headline with it - the
@@ -872,8 +909,7 @@ def main():
                                    "(%d MiB distinct, tiled with period %d B so that no two chunks are equal), %d device-layer call(s) of "
                                    "<= 4 GiB per direction, compress then decompress" % (args.mb, base_n >> 20, tile, ncalls),
                        "chunk": CHUNK, "ratio": round(ratio, 4), "parallelism": "chunks sharded over %d rank(s), "
-                       "no data-path collective in the timed region" % world,
-                       "compress_GBps": round(raw_total / tc / 1e9, 3), "decompress_GBps": round(raw_total / td / 1e9, 3)},
+                       "no data-path collective in the timed region" % world},
             "roofline": {"bound": "hbm", "kernel": "qzk_lz77_pull_kernel", "achieved": round(achieved, 3),
                          "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6),
                          "traffic": traffic, "algorithmic_bytes": int(alg_bytes),
@@ -887,7 +923,6 @@ def main():
                          "frac_of_measured_copy": round(achieved / copy_peak, 6) if copy_peak else None,
                          "launch_ms": round(launch_ms, 3), "launches": int(k1_launches),
                          "chunks_per_launch": round(k1_chunks / max(k1_launches, 1), 1),
-                         "full_launch_alone_ms": round(k_ms[0], 3), "full_launch_chunks": probe_n // CHUNK,
                          "fused": "K2 (Huffman coding) and the chunk CRC-32 run inside this kernel's waves",
                          # where this design stops (profiles/r5_k1_without_k2.txt): the same launch with K2
                          # compiled out - the parse and the CRC alone, measured once on an MI355X, not by this run
@@ -914,6 +949,9 @@ def main():
                                       "algorithmic_bytes": int(dec_alg), "launch_ms": round(dec_ms, 3),
                                       "phase_A_ms": round(inf_ms[3], 3), "phase_B_ms": round(inf_ms[2], 3),
                                       "inflate_step_ms_with_host_walk": round(inf_ms[0], 3), "call_MiB": call_n[-1] >> 20}
+        if args.full:
+            res["config"].update({"compress_GBps": round(raw_total / tc / 1e9, 3), "decompress_GBps": round(raw_total / td / 1e9, 3)})
+            res["roofline"].update({"full_launch_alone_ms": round(k_ms[0], 3), "full_launch_chunks": probe_n // CHUNK})
         res["config"].update(extra)
         if "pcie_h2d_GBps" in extra and "api_compress_GBps" in extra:
             # the host-to-host API against what bounds it: input over the link while the kernels run, output back
@@ -924,7 +962,7 @@ def main():
             res["config"]["ranks_share_devices"] = "%d ranks on %d device(s)" % (world, ndev)
         if one is not None:
             res["config"]["one_stream"] = one
-        if world > 1:
+        if args.full and world > 1:
             # what a SCALE record is read for, at the top level: every rank's own rates (its 4 GiB per direction) and what
             # the multi-GPU member costs (the gathers' share of a pass that no deflate ran beside)
             res["per_rank"] = {"compress_GBps": [round(total / r[0] / 1e9, 2) for r in per_rank],
@@ -935,7 +973,7 @@ def main():
                     if leg and "gather_share" in leg:
                         res.setdefault("one_stream_gather_share", {})[tr] = leg["gather_share"]
                         res.setdefault("one_stream_GBps", {})[tr] = leg.get("GBps", leg.get("value"))
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             res["cpu_baseline"] = cpu_baseline(args.cpu_mb, args.base_mb, args.cpu_threads)
         print(json.dumps(res), flush=True)
     if hard_exit:
