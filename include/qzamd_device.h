@@ -44,6 +44,9 @@ uint32_t qzd_batch_chunks(qzd_ctx *ctx);
 /* accumulated duration (HIP events on the launching stream), count and chunk total of the LZ77 kernel launches
  * since the last reset; harvested whenever qzd_sync() completes a compress call */
 int qzd_k1_stats(qzd_ctx *ctx, double *ms, uint64_t *launches, uint64_t *chunks, int reset);
+/* decode counters since the last reset: segments the K-lanes-per-segment phase A handed back to the serial phase A, and
+ * decode steps that handed back more segments than the hand-back area holds and were re-run with one lane a segment */
+int qzd_inflate_stats(qzd_ctx *ctx, uint64_t *handed_back_segments, uint64_t *k1_reruns, int reset);
 
 /* measured stream-copy rate of the device, read + written decimal GB per second (a hand-written 16-byte-per-lane copy
  * kernel over two buffers of `bytes` each, best of `iters`): the yardstick beside the 8 TB/s datasheet figure */

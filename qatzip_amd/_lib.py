@@ -34,6 +34,7 @@ def load(build_if_missing=True):
     L.qzd_last_error.argtypes = [vp]; L.qzd_last_error.restype = C.c_char_p
     L.qzd_batch_chunks.argtypes = [vp]; L.qzd_batch_chunks.restype = C.c_uint32
     L.qzd_k1_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]
+    L.qzd_inflate_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]
     L.qzd_stream_copy_peak.argtypes = [vp, C.c_uint64, C.c_int, C.POINTER(C.c_double)]
     L.qzd_dev_alloc.argtypes = [vp, C.c_size_t]; L.qzd_dev_alloc.restype = vp
     L.qzd_dev_free.argtypes = [vp, vp]
@@ -93,7 +94,7 @@ def exported_symbols():
             "qzd_h2d", "qzd_d2h", "qzd_host_alloc_pinned", "qzd_host_free_pinned", "qzd_deflate_raw",
             "qzd_deflate_raw_async", "qzd_sync", "qzd_result", "qzd_last_timing", "qzd_inflate_segments",
             "qzd_inflate_stream", "qzd_crc32", "qzd_crc32_ranges", "qzd_last_inflate_timing", "qzd_inflate_scratch_bytes",
-            "qzd_lz4_compress_frames", "qzd_lz4_compress_frames_hw", "qzd_lz4_decompress_frames", "qzd_chunk_lens", "qzd_batch_chunks", "qzd_k1_stats",
+            "qzd_lz4_compress_frames", "qzd_lz4_compress_frames_hw", "qzd_lz4_decompress_frames", "qzd_chunk_lens", "qzd_batch_chunks", "qzd_k1_stats", "qzd_inflate_stats",
             "qzd_adler32_chunks", "qzd_adler32_combine", "qzd_stream_copy_peak", "qzd_deflate_raw_from_host",
             "qzd_deflate_slots", "qzd_inflate_stream_to_host", "qzd_inflate_stream_from_host", "qzamd_async_stats", "qzd_shard_root_create",
             "qzd_shard_attach", "qzd_shard_slot_handle", "qzd_shard_attach_slot", "qzd_lz4_compress_linked", "qzd_shard_put", "qzd_shard_finish", "qzd_shard_close", "qzd_crc32_combine",
@@ -197,6 +198,12 @@ class Context:
         self.L.qzd_k1_stats(self.h, C.byref(ms), C.byref(ln), C.byref(ch), 1 if reset else 0)
         return ms.value, ln.value, ch.value
 
+    def inflate_stats(self, reset=False):
+        """(segments the K-lane phase A handed back, decode steps re-run with one lane a segment) since the last reset"""
+        hb, rr = C.c_uint64(0), C.c_uint64(0)
+        self._chk(self.L.qzd_inflate_stats(self.h, C.byref(hb), C.byref(rr), 1 if reset else 0))
+        return hb.value, rr.value
+
     def timing(self):
         ms = (C.c_float * 4)()
         self.L.qzd_last_timing(self.h, C.byref(ms))
@@ -204,8 +211,9 @@ class Context:
 
     # -- inflate
     def inflate_segments(self, d_comp, d_out, segs):
-        """segs: list of (in_off, out_off, in_len, out_cap, flags) -> structured result array"""
-        sa = np.array([tuple(s) + (0,) for s in segs], dtype=SEG_DT)
+        """segs: list of (in_off, out_off, in_len, out_cap, flags[, pad]) -> structured result array.  pad, when given, is
+        the segment's compressed length: with it on every segment the K-lanes-per-segment phase A may take them"""
+        sa = np.array([tuple(s) + (0,) * (6 - len(s)) for s in segs], dtype=SEG_DT)
         res = np.zeros(len(segs), RES_DT)
         self._chk(self.L.qzd_inflate_segments(self.h, d_comp.ptr, d_out.ptr, sa.ctypes.data, len(segs), res.ctypes.data))
         return res

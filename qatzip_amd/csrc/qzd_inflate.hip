@@ -254,6 +254,11 @@ static int two_phase(qzd_ctx *c, const uint8_t *d_comp, uint8_t *d_out, const qz
     const uint32_t R = K == 1 ? 0u : std::min<uint32_t>(nsegs, QZK_SPEC_HANDBACK(nsegs));
     const uint64_t hb0 = arena, hb_rg = QZK_TOK_REGION(max_cap);
     arena += (uint64_t)R * hb_rg;
+    /* sequences grow down from a region's end in 16-byte stores (qzk_inflate_lane.h): every region starts and ends 16-aligned */
+    bool aligned = ((hb0 | hb_rg) & 15) == 0;
+    if (uniform) for (uint32_t j = 0; j < K; j++) aligned &= ((F.pre[j] | F.len[j] | F.seg) & 15) == 0;
+    else for (size_t i = 0; i < (size_t)nsegs * K; i++) aligned &= ((tsv[i].lit_off & 15) | (tsv[i].seq_off & 1)) == 0;
+    if (!aligned) { snprintf(c->err, sizeof(c->err), "inflate: a token region is not 16-byte aligned"); return QZD_ERR_PARAM; }
     const size_t tabb = ((size_t)nsegs * sizeof(qzk_inf_tab) + 255) & ~(size_t)255;
     const size_t tsb = ((size_t)nsegs * K * sizeof(qzk_tokseg) + 255) & ~(size_t)255;
     const size_t chb = ((size_t)nsegs * sizeof(qzk_chain) + 255) & ~(size_t)255;
@@ -347,7 +352,8 @@ static int two_phase(qzd_ctx *c, const uint8_t *d_comp, uint8_t *d_out, const qz
         else { if (socc == 3) QZD_SPEC_LAUNCH(8, 3); else QZD_SPEC_LAUNCH(8, 2); }
 #undef QZD_SPEC_LAUNCH
         /* what that kernel hands back (QZK_INF_ESPEC: a sub-stream outgrew its scratch, too many pieces) goes through the
-         * serial phase A, into the segment's first sub-stream - which is sized for a whole segment */
+         * serial phase A, into one of the R whole-segment regions of the hand-back area behind the sub-streams (the K-lane
+         * regions are sized by need: lane 0's holds half a segment or less from K = 8 on) */
         HIPCHK(c, ctl_copy(st_res, d_res, rb, st));
         HIPCHK(c, hipStreamSynchronize(st));
         uint32_t nredo = 0;
@@ -359,7 +365,11 @@ static int two_phase(qzd_ctx *c, const uint8_t *d_comp, uint8_t *d_out, const qz
             for (int k = 0; k < 64; k++) if (hist[k]) fprintf(stderr, " %d:%u", k, hist[k]);
             fprintf(stderr, "\n");
         }
-        if (nredo > R) return two_phase(c, d_comp, d_out, hs, nsegs, h_res, 1, st, run_b);      /* more than the hand-back area holds: this data is not what K lanes are for */
+        c->inf_handback_acc += nredo;
+        if (nredo > R) {                                            /* more than the hand-back area holds: this data is not what K lanes are for */
+            c->inf_k1rerun_acc++;
+            return two_phase(c, d_comp, d_out, hs, nsegs, h_res, 1, st, run_b);
+        }
         res_fresh = nredo == 0;
         if (nredo) {
             if (uniform) fill_host();
@@ -482,6 +492,15 @@ static int two_phase_resolve(qzd_ctx *c, const uint8_t *d_comp, uint8_t *d_out, 
     memcpy(h_res, st_res, rb);
     float t = 0;
     if (hipEventElapsedTime(&t, c->ev[1][0], c->ev[1][2]) == hipSuccess) c->inf_ms[2] += t;
+    return QZD_OK;
+}
+
+extern "C" int qzd_inflate_stats(qzd_ctx *c, uint64_t *handed_back_segments, uint64_t *k1_reruns, int reset)
+{
+    if (!c) return QZD_ERR_PARAM;
+    if (handed_back_segments) *handed_back_segments = c->inf_handback_acc;
+    if (k1_reruns) *k1_reruns = c->inf_k1rerun_acc;
+    if (reset) { c->inf_handback_acc = 0; c->inf_k1rerun_acc = 0; }
     return QZD_OK;
 }
 

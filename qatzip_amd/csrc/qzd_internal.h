@@ -38,6 +38,9 @@ struct qzd_ctx {
     /* K1 launch durations (HIP events around every K1 launch, harvested at qzd_sync): bench.py's roofline input */
     hipEvent_t k1ev[QZD_K1EV][2]; uint32_t k1ev_chunks[QZD_K1EV]; uint32_t k1ev_n;
     double k1_ms_acc; uint64_t k1_launch_acc, k1_chunk_acc;
+    /* decode counters since the last reset (qzd_inflate_stats): segments the K-lane phase A handed back to the serial one,
+     * and two_phase() calls that handed back more than the hand-back area holds and were re-run with one lane a segment */
+    uint64_t inf_handback_acc, inf_k1rerun_acc;
     size_t slot_cap;
     /* per-call arrays */
     uint32_t *d_len, *d_crc; uint64_t *d_offs; uint32_t call_cap;

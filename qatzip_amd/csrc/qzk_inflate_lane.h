@@ -189,8 +189,13 @@ typedef struct { uint32_t nel, pad; qzk_chain_el el[QZK_CHAIN_MAXEL]; } qzk_chai
 /* scratch a segment needs: literals <= out_cap (+ staging slack), sequences <= out_cap / 3 (+ tail) */
 #define QZK_TOK_LITCAP(out_cap) ((((uint64_t)(out_cap) + 31) & ~(uint64_t)31) + 32)
 #define QZK_TOK_SEQCAP(out_cap) (((uint64_t)(out_cap) / 3 + 3) & ~(uint64_t)1)      /* even: sequences leave in aligned pairs */
-/* the region of a sub-stream that must hold a whole segment whatever it is made of (the one-lane kernel's): bytes, a multiple of 32 */
+/* the region of a sub-stream that must hold a whole segment whatever it is made of (the one-lane kernel's): bytes, a multiple of 16
+ * (the literals' part is one of 32, the sequences' eight bytes times an even count).  Sequences grow down from the region's end in
+ * 16-byte stores, so every region must end 16-aligned: the host checks (lit_off + region) % 16 == 0 for each one it lays out */
 #define QZK_TOK_REGION(out_cap) (QZK_TOK_LITCAP(out_cap) + 8 * QZK_TOK_SEQCAP(out_cap))
+static_assert(QZK_TOK_REGION(1) % 16 == 0 && QZK_TOK_REGION(1000) % 16 == 0 && QZK_TOK_REGION(16384 + 64) % 16 == 0 &&
+              QZK_TOK_REGION(65536) % 16 == 0 && QZK_TOK_REGION(65536 + 64) % 16 == 0 && QZK_TOK_REGION(131072 + 64) % 16 == 0 &&
+              QZK_TOK_REGION(524288 + 64) % 16 == 0 && QZK_TOK_REGION(0xffffffffu) % 16 == 0, "a sub-stream region must end 16-aligned");
 
 enum { QZK_LS_HDR = 0, QZK_LS_SYM, QZK_LS_RAW, QZK_LS_DONE };
 #ifndef QZK_LIT_RUN

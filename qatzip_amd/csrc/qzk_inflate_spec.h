@@ -76,6 +76,9 @@
 #define QZK_SPEC_MARGIN (96 + 512 + 8 * (10 + 64))
 #define QZK_SPEC_REGION(out_cap, K, j) ((((uint64_t)(out_cap) * QZK_SPEC_DENS8 / 8 * QZK_SPEC_SLACK8(K, j) / 8 / (K) + 63) & ~(uint64_t)63) + ((QZK_SPEC_MARGIN + 63) & ~63))
 #define QZK_SPEC_HANDBACK(nsegs) ((nsegs) / 32u > 64u ? (nsegs) / 32u : 64u)      /* whole-segment regions kept for the segments handed back */
+static_assert(QZK_SPEC_REGION(1, 4, 0) % 64 == 0 && QZK_SPEC_REGION(65536, 16, 0) % 64 == 0 && QZK_SPEC_REGION(65536 + 64, 8, 7) % 64 == 0 &&
+              QZK_SPEC_REGION(16384 + 64, 4, 3) % 64 == 0 && QZK_SPEC_REGION(524288 + 64, 32, 31) % 64 == 0 &&
+              QZK_SPEC_REGION(131072 + 64, 32, 5) % 64 == 0, "a K-lane sub-stream region is a multiple of 64 bytes");
 
 typedef struct __attribute__((aligned(32))) { uint32_t pos, nlit, nseq, lrun, olen, tag, pad0, pad1; } qzk_rec;     /* a mark: trip start (bit offset) and the token counters there */
 enum { QZK_ST_RUN = 0, QZK_ST_SYNC, QZK_ST_EOB, QZK_ST_REDO };
@@ -455,8 +458,9 @@ QZ_KERNEL_OCC(64, OCC) qzk_inflate_spec_kernel(const uint8_t *comp, const qzk_in
                 const bool broke = s.kind == QZK_ST_REDO && (s.cidx == 4u || ((s.cidx == 1u || s.cidx == 2u || s.cidx == 5u) && cur != 0));
                 if (s.kind != QZK_ST_SYNC && s.kind != QZK_ST_EOB && !broke) {
                     /* a lane on the chain decodes the true stream: what stopped it (cidx 3: bad data, the end of the input, the
-                     * capacity) is the segment's own error; lane 0 out of scratch (its sub-stream holds a whole segment) or
-                     * anything else is this kernel's */
+                     * capacity) is the segment's own error; lane 0 out of scratch (its sub-stream is sized by need, QZK_SPEC_REGION:
+                     * half a segment or less from K = 8 on, so flat codes or match-dense data overrun it) or anything else is this
+                     * kernel's, and the segment is handed back */
                     why = 10 + s.cidx; walking = false;
                     if (s.kind == QZK_ST_REDO && s.cidx == 3u) bad_status = (int)s.at;
                     continue;
@@ -470,7 +474,8 @@ QZ_KERNEL_OCC(64, OCC) qzk_inflate_spec_kernel(const uint8_t *comp, const qzk_in
                 onchain |= 1u << cur;
                 if (broke) {
                     /* the lane's sub-stream is full (or it ran past the input it was told of): its piece stands, and the block
-                     * goes on from where it stopped in a round of its own - lane 0's sub-stream has room for all of it */
+                     * goes on from where it stopped in a round of its own (no sub-stream holds a whole segment: one that runs
+                     * out of room there too hands the segment back) */
                     ok = true; cont = true; cont_at = s.at; cont_past = s.cidx == 1u; cont_grow = s.cidx == 4u;
                     c_last = h_last; c_lmax = h_lmax; c_dmax = h_dmax; c_lbase = h_lbase;
                     walking = false;
