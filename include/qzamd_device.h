@@ -196,6 +196,17 @@ int qzd_lz4_compress_frames_hw(qzd_ctx *ctx, const uint8_t *d_src, uint64_t n, u
  * liblz4 rescales its 32-bit positions, which is not reproduced) */
 int qzd_lz4_compress_linked(qzd_ctx *ctx, const uint8_t *d_src, uint64_t n, uint8_t *d_dst, uint64_t dst_cap,
                             uint64_t *h_out_len);
+/* comp_lvl 3-8 (liblz4's LZ4-HC hash-chain parser; 9-12 are not offered): the same three entry points with a `level`, byte
+ * for byte LZ4F_compressFrame at that level.  Every 64 KB block of every frame is parsed by a wave of its own - the blocks
+ * of a linked frame too, because LZ4-HC's chains do not depend on the parse (qzk_lz4hc.h) - in rounds of 4096 blocks;
+ * device-only scratch of about 7 bytes per input byte of a round (1.8 GiB at most) is kept by the context.
+ * qzd_lz4hc_compress_frames: frame_sz <= 64 KB; _hw: frame_sz <= 1 GiB; _linked: 64 KB < n <= 0x7fff0000. */
+int qzd_lz4hc_compress_frames(qzd_ctx *ctx, const uint8_t *d_src, uint64_t n, uint32_t frame_sz, int level, uint8_t *d_dst,
+                              uint64_t dst_cap, uint64_t *h_out_len, uint32_t *h_frame_len);
+int qzd_lz4hc_compress_frames_hw(qzd_ctx *ctx, const uint8_t *d_src, uint64_t n, uint32_t frame_sz, int level, uint8_t *d_dst,
+                                 uint64_t dst_cap, uint64_t *h_out_len, uint32_t *h_frame_len);
+int qzd_lz4hc_compress_linked(qzd_ctx *ctx, const uint8_t *d_src, uint64_t n, int level, uint8_t *d_dst, uint64_t dst_cap,
+                              uint64_t *h_out_len);
 /* decode nsegs frames (any block mode, content checksum verified on the GPU); replaces LZ4F_decompress,
  * src/qatzip_sw.c:496 */
 int qzd_lz4_decompress_frames(qzd_ctx *ctx, const uint8_t *d_comp, uint8_t *d_out, const void *h_segs,

@@ -59,6 +59,9 @@ def load(build_if_missing=True):
     L.qzd_lz4_compress_frames_hw.argtypes = L.qzd_lz4_compress_frames.argtypes
     L.qzd_lz4_compress_linked.argtypes = [vp, u8p, C.c_uint64, u8p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.qzd_lz4_decompress_frames.argtypes = [vp, u8p, u8p, vp, C.c_uint32, vp]
+    L.qzd_lz4hc_compress_frames.argtypes = [vp, u8p, C.c_uint64, C.c_uint32, C.c_int, u8p, C.c_uint64, C.POINTER(C.c_uint64), vp]
+    L.qzd_lz4hc_compress_frames_hw.argtypes = L.qzd_lz4hc_compress_frames.argtypes
+    L.qzd_lz4hc_compress_linked.argtypes = [vp, u8p, C.c_uint64, C.c_int, u8p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.qzd_chunk_lens.argtypes = [vp, vp, C.c_uint32]
     L.qzd_shard_root_create.argtypes = [vp, C.c_uint32, C.c_uint64, C.c_char_p, C.POINTER(vp)]
     L.qzd_shard_attach.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_char_p, C.c_uint64, C.POINTER(vp)]
@@ -98,6 +101,7 @@ def exported_symbols():
             "qzd_adler32_chunks", "qzd_adler32_combine", "qzd_stream_copy_peak", "qzd_deflate_raw_from_host",
             "qzd_deflate_slots", "qzd_inflate_stream_to_host", "qzd_inflate_stream_from_host", "qzamd_async_stats", "qzd_shard_root_create",
             "qzd_shard_attach", "qzd_shard_slot_handle", "qzd_shard_attach_slot", "qzd_lz4_compress_linked", "qzd_shard_put", "qzd_shard_finish", "qzd_shard_close", "qzd_crc32_combine",
+            "qzd_lz4hc_compress_frames", "qzd_lz4hc_compress_frames_hw", "qzd_lz4hc_compress_linked",
             "qzd_crc32_fold", "qzd_pcie_peak", "qzd_rccl_unique_id", "qzd_rccl_create", "qzd_rccl_gather", "qzd_rccl_close"]
 
 
@@ -231,14 +235,28 @@ class Context:
         return crc.value
 
     # -- LZ4
-    def lz4_compress_frames(self, d_src, n, d_dst, frame_sz=65536):
-        """-> (out_len, per-frame lengths)"""
+    def lz4_compress_frames(self, d_src, n, d_dst, frame_sz=65536, level=1, hw=False):
+        """-> (out_len, per-frame lengths).  level 1-2: liblz4's fast parser, 3-8: LZ4-HC (qzd_lz4hc_*); hw: the hardware
+        path's header per frame (frame_sz may then exceed 64 KB: linked blocks)"""
         nfr = max(1, (n + frame_sz - 1) // frame_sz)
         ol = C.c_uint64(0)
         lens = np.zeros(nfr, np.uint32)
-        self._chk(self.L.qzd_lz4_compress_frames(self.h, d_src.ptr, n, frame_sz, d_dst.ptr, d_dst.nbytes, C.byref(ol),
-                                                 lens.ctypes.data))
+        if level >= 3:
+            fn = self.L.qzd_lz4hc_compress_frames_hw if hw else self.L.qzd_lz4hc_compress_frames
+            self._chk(fn(self.h, d_src.ptr, n, frame_sz, level, d_dst.ptr, d_dst.nbytes, C.byref(ol), lens.ctypes.data))
+        else:
+            fn = self.L.qzd_lz4_compress_frames_hw if hw else self.L.qzd_lz4_compress_frames
+            self._chk(fn(self.h, d_src.ptr, n, frame_sz, d_dst.ptr, d_dst.nbytes, C.byref(ol), lens.ctypes.data))
         return ol.value, lens
+
+    def lz4_compress_linked(self, d_src, n, d_dst, level=1):
+        """one call above 64 KB as the ONE frame of linked blocks LZ4F_compressFrame writes for it -> out_len"""
+        ol = C.c_uint64(0)
+        if level >= 3:
+            self._chk(self.L.qzd_lz4hc_compress_linked(self.h, d_src.ptr, n, level, d_dst.ptr, d_dst.nbytes, C.byref(ol)))
+        else:
+            self._chk(self.L.qzd_lz4_compress_linked(self.h, d_src.ptr, n, d_dst.ptr, d_dst.nbytes, C.byref(ol)))
+        return ol.value
 
     def lz4_decompress_frames(self, d_comp, d_out, segs):
         """segs: list of (in_off, out_off, in_len, out_cap) -> structured results (status, in_used, out_len)"""

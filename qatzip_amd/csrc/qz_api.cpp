@@ -566,7 +566,8 @@ static int compress_lz4_hw(QzSession_T *sess, Sess *s, const unsigned char *src,
 {
     const uint32_t n = *src_len, cap = *dest_len, hw = s->p.hw_buff_sz;
     *src_len = 0; *dest_len = 0;
-    if (s->p.comp_lvl >= 3) return QZ_NOT_SUPPORTED;
+    const unsigned lvl = s->p.comp_lvl;
+    if (lvl >= 9) return QZ_NOT_SUPPORTED;                         /* 9: pattern analysis, 10-12: the optimal parser - not restated */
     const uint32_t nchunks = (n + hw - 1) / hw;
     const uint64_t per = 15 + 4ull * ((hw + 65535) >> 16) + hw + 8;       /* header, block headers, stored blocks, footer */
     int rc = reserve(s, n, (uint64_t)nchunks * per + 64);
@@ -575,7 +576,8 @@ static int compress_lz4_hw(QzSession_T *sess, Sess *s, const unsigned char *src,
     std::vector<uint32_t> lens(nchunks);
     uint64_t produced = 0;
     /* one launch for all chunks, whatever hw_buff_sz: one-block frames up to 64 KB, linked blocks above (a wave per chunk) */
-    if (qzd_lz4_compress_frames_hw(s->ctx, s->d_in, n, hw, s->d_out, s->out_cap, &produced, lens.data()) != QZD_OK) return QZ_FAIL;
+    if (lvl >= 3) { if (qzd_lz4hc_compress_frames_hw(s->ctx, s->d_in, n, hw, (int)lvl, s->d_out, s->out_cap, &produced, lens.data()) != QZD_OK) return QZ_FAIL; }
+    else if (qzd_lz4_compress_frames_hw(s->ctx, s->d_in, n, hw, s->d_out, s->out_cap, &produced, lens.data()) != QZD_OK) return QZ_FAIL;
     uint32_t take = 0; uint64_t bytes = 0;
     while (take < nchunks && bytes + lens[take] <= cap) bytes += lens[take++];
     if (take == 0) return QZ_BUF_ERROR;
@@ -598,7 +600,10 @@ static int compress_lz4(QzSession_T *sess, Sess *s, const unsigned char *src, un
      * want throughput make calls of at most 64 KB, like the reference's own harness (test/main.c:2204-2231) and its
      * hardware path, whose chunks are frames of their own (src/qatzip_lz4.c:104-132).  Only past 0x7fff0000 bytes, where
      * liblz4 starts rescaling its 32-bit positions, the call is written as one independent frame per 64 KB instead. */
-    if (s->p.comp_lvl >= 3) return QZ_NOT_SUPPORTED;               /* level >= 3 is LZ4-HC in liblz4 */
+    /* comp_lvl 3-8 is liblz4's LZ4-HC hash-chain parser: the same frames, every block parsed by a wave of its own
+     * (qzd_lz4hc_*); 9 (pattern analysis) and 10-12 (the optimal parser) are not restated and must not run as a lower level */
+    const unsigned lvl = s->p.comp_lvl;
+    if (lvl >= 9) return QZ_NOT_SUPPORTED;
     const bool linked = n > 65536 && n <= 0x7fff0000u;
     const uint64_t nfr = n ? ((uint64_t)n + 65535) >> 16 : 1;
     const uint64_t bound = linked ? 19 + 4 * nfr + (uint64_t)n + 8 : nfr * (19 + 4 + 8) + (uint64_t)n;   /* LZ4F_compressFrameBound */
@@ -607,7 +612,11 @@ static int compress_lz4(QzSession_T *sess, Sess *s, const unsigned char *src, un
     if (rc) return rc;
     if (n && qzd_h2d(s->ctx, s->d_in, src, n) != QZD_OK) return QZ_FAIL;
     uint64_t produced = 0;
-    if (linked) { if (qzd_lz4_compress_linked(s->ctx, s->d_in, n, s->d_out, s->out_cap, &produced) != QZD_OK) return QZ_FAIL; }
+    if (lvl >= 3) {
+        if (linked) { if (qzd_lz4hc_compress_linked(s->ctx, s->d_in, n, (int)lvl, s->d_out, s->out_cap, &produced) != QZD_OK) return QZ_FAIL; }
+        else if (qzd_lz4hc_compress_frames(s->ctx, s->d_in, n, 65536, (int)lvl, s->d_out, s->out_cap, &produced, NULL) != QZD_OK) return QZ_FAIL;
+    }
+    else if (linked) { if (qzd_lz4_compress_linked(s->ctx, s->d_in, n, s->d_out, s->out_cap, &produced) != QZD_OK) return QZ_FAIL; }
     else if (qzd_lz4_compress_frames(s->ctx, s->d_in, n, 65536, s->d_out, s->out_cap, &produced, NULL) != QZD_OK) return QZ_FAIL;
     if (qzd_d2h(s->ctx, dest, s->d_out, produced) != QZD_OK) return QZ_FAIL;
     *src_len = n; *dest_len = (unsigned int)produced;

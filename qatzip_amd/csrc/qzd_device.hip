@@ -1208,6 +1208,117 @@ extern "C" int qzd_lz4_compress_linked(qzd_ctx *c, const uint8_t *d_src, uint64_
     return QZD_OK;
 }
 
+/* ------------------------------------------------------------------ LZ4-HC frames (comp_lvl 3-8: H1 / H2 / H3) */
+#include "qzk_lz4hc.h"
+#define QZD_HC_BATCH 4096u          /* blocks per round: 128 KiB of head table, 256 KiB of chain distances and a slot each, ~7 bytes of scratch per input byte */
+
+/* every frame_sz bytes of d_src become the frame LZ4F_compressFrame writes for them at `level` (3-8: liblz4's hash-chain
+ * parser): one independent block up to 64 KB, linked 64 KB blocks above.  All blocks of all frames are parsed side by side,
+ * a wave each, in rounds of QZD_HC_BATCH blocks; scratch comes from the context's device-only pool (as the lazy deflate
+ * levels' does). */
+static int lz4hc_impl(qzd_ctx *c, const uint8_t *d_src, uint64_t n, uint32_t frame_sz, int level, uint32_t hw_hdr,
+                      uint8_t *d_dst, uint64_t dst_cap, uint64_t *h_out_len, uint32_t *h_frame_len)
+{
+    if (!c || !d_dst || (n && !d_src) || !h_out_len) return QZD_ERR_PARAM;
+    if (level < 3 || level > 8) { snprintf(c->err, sizeof(c->err), "LZ4-HC: levels 3-8 (level %d asked for)", level); return QZD_ERR_UNSUPPORTED; }
+    if (frame_sz == 0 || frame_sz > 0x7fff0000u || n > 0xffffffffull) { snprintf(c->err, sizeof(c->err), "LZ4-HC frames: 0 < frame_sz <= 0x7fff0000, n < 4 GiB"); return QZD_ERR_UNSUPPORTED; }
+    const int attempts = 4 << (level - 3);                          /* lz4hc.c clTable: 4, 8, 16, 32, 64, 128 */
+    hipSetDevice(c->device);
+    const uint32_t bpf = (frame_sz + QZK_LZ4_MAXBLK - 1) / QZK_LZ4_MAXBLK;
+    const uint32_t nfr = n ? (uint32_t)((n + frame_sz - 1) / frame_sz) : 1;
+    const uint64_t lastlen = n - (uint64_t)(nfr - 1) * frame_sz;
+    const uint64_t nb64 = (uint64_t)(nfr - 1) * bpf + (lastlen ? (lastlen + QZK_LZ4_MAXBLK - 1) / QZK_LZ4_MAXBLK : 1);
+    if (nb64 > 0x7fffffffull) { snprintf(c->err, sizeof(c->err), "LZ4-HC frames: too many blocks"); return QZD_ERR_UNSUPPORTED; }
+    const uint32_t nb = (uint32_t)nb64;
+    const uint32_t stride = (QZK_LZ4_MAXBLK + QZK_HC_HDRMAX + 4 + 8 + 15) & ~15u;
+    const uint32_t B = nb < QZD_HC_BATCH ? nb : QZD_HC_BATCH;
+    const size_t headb = (size_t)B * QZK_HC_HSIZE * 4, chainb = (size_t)B * QZK_HC_WIN * 2, slotb = (size_t)B * stride;
+    const size_t need = headb + chainb + slotb;
+    if (need > c->lane_cap) {
+        hipDeviceSynchronize();
+        if (c->d_lane) hipFree(c->d_lane);
+        c->d_lane = NULL; c->lane_cap = 0;
+        HIPCHK(c, hipMalloc(&c->d_lane, need));
+        c->lane_cap = need;
+    }
+    if (nb > c->call_cap) {
+        hipDeviceSynchronize();
+        hipFree(c->d_len); hipFree(c->d_crc); hipFree(c->d_offs);
+        c->d_len = NULL; c->d_crc = NULL; c->d_offs = NULL; c->call_cap = 0;
+        HIPCHK(c, hipMalloc(&c->d_len, (size_t)nb * 4));
+        HIPCHK(c, hipMalloc(&c->d_crc, (size_t)nb * 4));
+        HIPCHK(c, hipMalloc(&c->d_offs, QZD_OFFS_BYTES(nb)));
+        c->call_cap = nb;
+    }
+    uint32_t *head = (uint32_t *)c->d_lane;
+    uint16_t *chain = (uint16_t *)(c->d_lane + headb);
+    uint8_t *slots = c->d_lane + headb + chainb;
+    uint32_t *xx = c->d_crc;                                        /* one content hash per frame (nfr <= nb) */
+    hipStream_t st = c->st[0];
+    HIPCHK(c, hipMemsetAsync(c->d_running, 0, 8, st));
+    HIPCHK(c, hipMemsetAsync(c->d_overflow, 0, 4, st));
+    HIPCHK(c, hipEventRecord(c->ev_begin, st));
+    /* the content checksums on a stream of their own: a frame's XXH32 is one wave's serial work (a gigabyte takes most of a
+     * second), the rounds below go on beside it and only the finish kernel waits for it */
+    HIPCHK(c, hipStreamWaitEvent(c->st[1], c->ev_begin, 0));
+    hipLaunchKernelGGL(qzk_lz4hc_xxh_kernel, dim3(nfr), dim3(64), 0, c->st[1], d_src, n, frame_sz, nfr, xx);
+    HIPCHK(c, hipEventRecord(c->done[1], c->st[1]));
+    for (uint32_t g0 = 0; g0 < nb; g0 += B) {
+        const uint32_t bn = nb - g0 < B ? nb - g0 : B;
+        HIPCHK(c, hipMemsetAsync(head, 0, (size_t)bn * QZK_HC_HSIZE * 4, st));
+        hipLaunchKernelGGL(qzk_lz4hc_chain_kernel, dim3(bn), dim3(64), 0, st, d_src, n, frame_sz, bpf, g0, bn, head, chain);
+        hipLaunchKernelGGL(qzk_lz4hc_parse_kernel, dim3(bn), dim3(64), 0, st, d_src, n, frame_sz, bpf, g0, bn,
+                           (const uint16_t *)chain, slots, stride, c->d_len + g0, hw_hdr, attempts);
+        hipLaunchKernelGGL(qzk_scan_kernel, dim3(1), dim3(1024), 0, st, c->d_len + g0, bn, c->d_offs + g0, c->d_running);
+        hipLaunchKernelGGL(qzk_gather_kernel, dim3(bn), dim3(256), 0, st, slots, stride, c->d_len + g0, c->d_offs + g0, bn, d_dst, dst_cap, c->d_overflow);
+    }
+    /* end marks and checksums of all frames at once, behind the last round and behind the hashes */
+    HIPCHK(c, hipStreamWaitEvent(st, c->done[1], 0));
+    hipLaunchKernelGGL(qzk_lz4hc_finish_kernel, dim3((nfr + 63) / 64), dim3(64), 0, st, n, frame_sz, bpf, 0u, nb, nb,
+                       (const uint64_t *)c->d_offs, (const uint32_t *)c->d_len, (const uint32_t *)xx, d_dst, dst_cap);
+    HIPCHK(c, hipEventRecord(c->ev_end, st));
+    HIPCHK(c, hipMemcpyAsync(c->h_running, c->d_running, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(c->h_overflow, c->d_overflow, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, hipGetLastError());
+    c->last_nchunks = nb;
+    if (*c->h_overflow) { snprintf(c->err, sizeof(c->err), "destination too small"); return QZD_ERR_DSTCAP; }
+    *h_out_len = *c->h_running;
+    if (h_frame_len) {
+        std::vector<uint32_t> bl(nb);
+        HIPCHK(c, hipMemcpy(bl.data(), c->d_len, (size_t)nb * 4, hipMemcpyDeviceToHost));
+        for (uint32_t f = 0; f < nfr; f++) {
+            uint32_t sum = 0;
+            for (uint64_t g = (uint64_t)f * bpf; g < (uint64_t)(f + 1) * bpf && g < nb; g++) sum += bl[g];
+            h_frame_len[f] = sum;
+        }
+    }
+    float t = 0;
+    if (hipEventElapsedTime(&t, c->ev_begin, c->ev_end) == hipSuccess) c->ms[3] = t;
+    return QZD_OK;
+}
+extern "C" int qzd_lz4hc_compress_frames(qzd_ctx *c, const uint8_t *d_src, uint64_t n, uint32_t frame_sz, int level,
+                                         uint8_t *d_dst, uint64_t dst_cap, uint64_t *h_out_len, uint32_t *h_frame_len)
+{
+    if (c && frame_sz > QZK_LZ4_MAXBLK) { snprintf(c->err, sizeof(c->err), "LZ4 frames above 64 KB (linked blocks) are not produced"); return QZD_ERR_UNSUPPORTED; }
+    return lz4hc_impl(c, d_src, n, frame_sz, level, 0, d_dst, dst_cap, h_out_len, h_frame_len);
+}
+extern "C" int qzd_lz4hc_compress_frames_hw(qzd_ctx *c, const uint8_t *d_src, uint64_t n, uint32_t frame_sz, int level,
+                                            uint8_t *d_dst, uint64_t dst_cap, uint64_t *h_out_len, uint32_t *h_frame_len)
+{
+    if (c && frame_sz > (1u << 30)) { snprintf(c->err, sizeof(c->err), "LZ4 frames above 64 KB (linked blocks) are not produced"); return QZD_ERR_UNSUPPORTED; }
+    return lz4hc_impl(c, d_src, n, frame_sz, level, 1, d_dst, dst_cap, h_out_len, h_frame_len);
+}
+extern "C" int qzd_lz4hc_compress_linked(qzd_ctx *c, const uint8_t *d_src, uint64_t n, int level, uint8_t *d_dst, uint64_t dst_cap,
+                                         uint64_t *h_out_len)
+{
+    if (!c || !d_src || !d_dst || !h_out_len) return QZD_ERR_PARAM;
+    if (n <= QZK_LZ4_MAXBLK || n > 0x7fff0000ull) { snprintf(c->err, sizeof(c->err), "linked LZ4 frames: 64 KB < n <= 0x7fff0000"); return QZD_ERR_UNSUPPORTED; }
+    const uint64_t bound = 19 + 4 * ((n + 65535) >> 16) + n + 8;
+    if (dst_cap < bound) { snprintf(c->err, sizeof(c->err), "destination too small"); return QZD_ERR_DSTCAP; }
+    return lz4hc_impl(c, d_src, n, (uint32_t)n, level, 0, d_dst, dst_cap, h_out_len, NULL);
+}
+
 /* decode nsegs LZ4 frames {u64 in_off, u64 out_off, u32 in_len, u32 out_cap} -> {i32 status, u32 in_used, u32 out_len, u32 pad};
  * content checksums are verified on the GPU (XXH32) */
 extern "C" int qzd_lz4_decompress_frames(qzd_ctx *c, const uint8_t *d_comp, uint8_t *d_out, const void *h_segs,
