@@ -2,9 +2,9 @@
  * qzd_device.hip — host side of the device-resident C ABI (include/qzamd_device.h)
  * and the small utility kernels (size scan, slot gather).  gfx950 only.
  *
- * Level 1, input already in HBM: ONE launch of qzk_lz77_pull_kernel over all chunks of the call (persistent 16-wave
- * workgroups, one per CU, every wave pulling chunk numbers; the waves of a workgroup share the lines of one epoch-tagged
- * candidate table).  The wave that parsed a chunk (K1) also codes it (K2, qzk_huff_chunk) into the chunk's slot and folds
+ * Level 1, input already in HBM: ONE launch of qzk_lz77_pull_kernel over all chunks of the call (persistent workgroups of
+ * QZK_K1_WAVES = 4 waves, QZK_K1_OCC = 5 to a CU, every wave pulling chunk numbers; the waves of a workgroup share the lines
+ * of one epoch-tagged candidate table).  The wave that parsed a chunk (K1) also codes it (K2, qzk_huff_chunk) into the chunk's slot and folds
  * its CRC-32 along the input reads; then
  *   scan of the lengths (running total carried in HBM, no host round trip)
  *   gather of the slots into the contiguous destination.
@@ -22,6 +22,8 @@
 #include <string.h>
 #include <new>
 #include <atomic>
+#include <algorithm>
+#include <vector>
 
 #include "qzd_internal.h"
 #include "qzk_deflate_huff.h"
@@ -265,8 +267,8 @@ extern "C" void qzd_destroy(qzd_ctx *c)
     if (!c) return;
     hipSetDevice(c->device);
     hipDeviceSynchronize();
+    hipFree(c->lz4_slots);
     for (int i = 0; i < QZD_NBUF; i++) {
-        hipFree(c->slots[i]);
         /* handles may be missing: qzd_create comes here from its failure paths */
         if (c->st[i] && !(c->helper && i > 0)) hipStreamDestroy(c->st[i]);
         if (c->done[i]) hipEventDestroy(c->done[i]);
@@ -414,9 +416,109 @@ static bool k1_fused(void)
     return fuse;
 }
 
+/* ------------------------------------------------------------------ the steps every compress path is made of */
+#define QZD_TRY(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)
+
+/* a device buffer that only grows: one that is too small is replaced (its contents are scratch) */
+static int grow_dev(qzd_ctx *c, void **p, size_t *cap, size_t need)
+{
+    if (need <= *cap) return QZD_OK;
+    hipDeviceSynchronize();
+    if (*p) hipFree(*p);
+    *p = NULL; *cap = 0;
+    HIPCHK(c, hipMalloc(p, need));
+    *cap = need;
+    return QZD_OK;
+}
+
+/* the per-call arrays for n chunks / frames / blocks: a length and a CRC each, and the offsets with what a launch that
+ * moves the stream itself keeps behind them (QZD_OFFS_BYTES) - whichever path allocated them, every other may use them */
+static int reserve_call_arrays(qzd_ctx *c, uint32_t n)
+{
+    if (n <= c->call_cap) return QZD_OK;
+    hipDeviceSynchronize();
+    hipFree(c->d_len); hipFree(c->d_crc); hipFree(c->d_offs);
+    c->d_len = NULL; c->d_crc = NULL; c->d_offs = NULL; c->call_cap = 0;
+    HIPCHK(c, hipMalloc(&c->d_len, (size_t)n * 4));
+    HIPCHK(c, hipMalloc(&c->d_crc, (size_t)n * 4));
+    HIPCHK(c, hipMalloc(&c->d_offs, QZD_OFFS_BYTES(n)));
+    c->call_cap = n;
+    return QZD_OK;
+}
+
+/* what a parse kernel hands to K2 for a round of chunks - a literal / length byte and a distance per input byte, the block
+ * marks - and K2's output slots */
+struct qzd_symbufs { uint8_t *sym_lc; uint16_t *sym_dist; qzk_lzmeta *meta; uint8_t *slots; };
+static size_t sym_bytes(uint32_t B, uint32_t chunk_sz) { return ((size_t)B * chunk_sz + 511) & ~(size_t)255; }
+/* ... for B chunks of chunk_sz out of d_lane, in pieces of 256 bytes, with `own` bytes behind them for the path's own
+ * tables (*tail = their first byte); d_lane grows to hold it all */
+static int carve_symbols(qzd_ctx *c, uint32_t B, uint32_t chunk_sz, size_t own, qzd_symbufs *y, uint8_t **tail)
+{
+    const size_t symb = sym_bytes(B, chunk_sz);
+    const size_t metab = ((size_t)B * sizeof(qzk_lzmeta) + 255) & ~(size_t)255;
+    const size_t slotb = ((size_t)B * slot_stride_for(chunk_sz) + 255) & ~(size_t)255;
+    QZD_TRY(grow_dev(c, (void **)&c->d_lane, &c->lane_cap, 3 * symb + metab + slotb + own));
+    uint8_t *pb = c->d_lane;
+    y->sym_lc = pb; pb += symb;
+    y->sym_dist = (uint16_t *)pb; pb += 2 * symb;
+    y->meta = (qzk_lzmeta *)pb; pb += metab;
+    y->slots = pb; pb += slotb;
+    *tail = pb;
+    return QZD_OK;
+}
+
+/* opens a call on st: what qzd_result / qzd_last_timing will ask about, the running total and the overflow word cleared */
+static int call_begin(qzd_ctx *c, hipStream_t st, uint32_t nchunks, uint32_t nbatches)
+{
+    c->last_nchunks = nchunks; c->nbatches = nbatches; c->k1ev_n = 0;
+    HIPCHK(c, hipMemsetAsync(c->d_running, 0, 8, st));
+    HIPCHK(c, hipMemsetAsync(c->d_overflow, 0, 4, st));
+    HIPCHK(c, hipEventRecord(c->ev_begin, st));
+    return QZD_OK;
+}
+
+/* the totals to the pinned words the host reads after the call, behind everything on st */
+static int publish_totals(qzd_ctx *c, hipStream_t st)
+{
+    HIPCHK(c, hipMemcpyAsync(c->h_running, c->d_running, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(c->h_overflow, c->d_overflow, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipGetLastError());
+    return QZD_OK;
+}
+
+/* K2 and the chunk CRCs as launches of their own, for the bn chunks from chunk b of the call (src, blen, cd: from that
+ * chunk on): every path but the fused K1 */
+static void launch_huff_crc(qzd_ctx *c, hipStream_t st, const uint8_t *src, uint64_t blen, uint32_t chunk_sz, uint32_t bn,
+                            const qzd_symbufs &y, uint32_t final_chunk, uint32_t b, const uint32_t *cd)
+{
+    hipLaunchKernelGGL(qzk_huff_kernel, dim3(bn), dim3(QZK_HW), 0, st, src, blen, chunk_sz, bn, y.sym_lc, y.sym_dist,
+                       y.meta, y.slots, slot_stride_for(chunk_sz), final_chunk, c->d_len + b, cd);
+    hipLaunchKernelGGL(qzk_crc_chunks_kernel, dim3(bn), dim3(QZK_HT), 0, st, src, blen, chunk_sz, bn, c->d_crc + b, cd);
+}
+
+/* the bn slots from chunk / frame / block b of the call to their places in the destination, behind what is there already */
+static void launch_scan_gather(qzd_ctx *c, hipStream_t st, const uint8_t *slots, uint32_t stride, uint32_t b, uint32_t bn,
+                               uint8_t *d_dst, uint64_t dst_cap)
+{
+    hipLaunchKernelGGL(qzk_scan_kernel, dim3(1), dim3(1024), 0, st, c->d_len + b, bn, c->d_offs + b, c->d_running);
+    hipLaunchKernelGGL(qzk_gather_kernel, dim3(bn), dim3(256), 0, st, slots, stride, c->d_len + b, c->d_offs + b, bn,
+                       d_dst, dst_cap, c->d_overflow);
+}
+
+/* the end of a call that returns its result: wait for st, then the overflow word and the total */
+static int finish_sync_call(qzd_ctx *c, hipStream_t st, uint64_t *h_out_len)
+{
+    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, hipGetLastError());
+    if (*c->h_overflow) { snprintf(c->err, sizeof(c->err), "destination too small"); return QZD_ERR_DSTCAP; }
+    *h_out_len = *c->h_running;
+    return QZD_OK;
+}
+
 /* the device pool's scratch (called with the pool's lock held) and this context's per-call arrays.
  *   fused:    symbols per WAVE (a wave codes the chunk it parsed before it pulls the next: 3 bytes per input byte for the
- *             4096 resident waves, whatever the call's size), slots and meta per chunk of the CALL, one set;
+ *             5120 resident waves - QZK_K1_WAVES x QZK_K1_OCC per CU -, whatever the call's size), slots and meta per chunk
+ *             of the CALL, one set;
  *   separate: symbols, slots and meta per chunk of a BATCH, double-buffered (K2 of batch b beside K1 of batch b+1). */
 static int ensure_scratch(qzd_ctx *c, qzd_k1pool *pool, uint32_t chunk_sz, uint32_t nchunks)
 {
@@ -440,16 +542,7 @@ static int ensure_scratch(qzd_ctx *c, qzd_k1pool *pool, uint32_t chunk_sz, uint3
         }
         pool->sym_cap = sym; pool->slot_cap = slot; pool->meta_cap = batch;
     }
-    if (nchunks > c->call_cap) {
-        hipDeviceSynchronize();
-        hipFree(c->d_len); hipFree(c->d_crc); hipFree(c->d_offs);
-        c->d_len = NULL; c->d_crc = NULL; c->d_offs = NULL; c->call_cap = 0;
-        HIPCHK(c, hipMalloc(&c->d_len, (size_t)nchunks * 4));
-        HIPCHK(c, hipMalloc(&c->d_crc, (size_t)nchunks * 4));
-        HIPCHK(c, hipMalloc(&c->d_offs, QZD_OFFS_BYTES(nchunks)));
-        c->call_cap = nchunks;
-    }
-    return QZD_OK;
+    return reserve_call_arrays(c, nchunks);
 }
 
 #include "qzk_deflate_lz77_lane.h"
@@ -459,40 +552,13 @@ static int ensure_scratch(qzd_ctx *c, qzd_k1pool *pool, uint32_t chunk_sz, uint3
 static int deflate_lane_path(qzd_ctx *c, const uint8_t *d_src, uint64_t n, uint32_t chunk_sz, int level, int last,
                              uint8_t *d_dst, uint64_t dst_cap, uint32_t nchunks, const uint32_t *cdesc)
 {
-    const uint32_t stride = slot_stride_for(chunk_sz);
-    const size_t symb = ((size_t)nchunks * chunk_sz + 511) & ~(size_t)255;
-    const size_t metab = ((size_t)nchunks * sizeof(qzk_lzmeta) + 255) & ~(size_t)255;
-    const size_t slotb = (size_t)nchunks * stride;
     const size_t headb = (size_t)nchunks * QZK_HSIZE * 2, prevb = (size_t)nchunks * QZK_WSIZE * 2;
-    const size_t need = symb * 3 + metab + slotb + headb + prevb;
-    if (need > c->lane_cap) {
-        hipDeviceSynchronize();
-        if (c->d_lane) hipFree(c->d_lane);
-        c->d_lane = NULL; c->lane_cap = 0;
-        HIPCHK(c, hipMalloc(&c->d_lane, need));
-        c->lane_cap = need;
-    }
-    if (nchunks > c->call_cap) {
-        hipDeviceSynchronize();
-        hipFree(c->d_len); hipFree(c->d_crc); hipFree(c->d_offs);
-        c->d_len = NULL; c->d_crc = NULL; c->d_offs = NULL; c->call_cap = 0;
-        HIPCHK(c, hipMalloc(&c->d_len, (size_t)nchunks * 4));
-        HIPCHK(c, hipMalloc(&c->d_crc, (size_t)nchunks * 4));
-        HIPCHK(c, hipMalloc(&c->d_offs, QZD_OFFS_BYTES(nchunks)));
-        c->call_cap = nchunks;
-    }
-    uint8_t *pb = c->d_lane;
-    uint8_t *sym_lc = pb; pb += symb;
-    uint16_t *sym_dist = (uint16_t *)pb; pb += 2 * symb;
-    qzk_lzmeta *meta = (qzk_lzmeta *)pb; pb += metab;
-    uint8_t *slots = pb; pb += slotb;
-    uint16_t *head = (uint16_t *)pb; pb += headb;
-    uint16_t *prev = (uint16_t *)pb;
+    qzd_symbufs y; uint8_t *own;
+    QZD_TRY(carve_symbols(c, nchunks, chunk_sz, headb + prevb, &y, &own));
+    QZD_TRY(reserve_call_arrays(c, nchunks));
+    uint16_t *head = (uint16_t *)own, *prev = (uint16_t *)(own + headb);
     hipStream_t st = c->st[0];
-    c->last_nchunks = nchunks; c->nbatches = 1;
-    HIPCHK(c, hipMemsetAsync(c->d_running, 0, 8, st));
-    HIPCHK(c, hipMemsetAsync(c->d_overflow, 0, 4, st));
-    HIPCHK(c, hipEventRecord(c->ev_begin, st));
+    QZD_TRY(call_begin(c, st, nchunks, 1));
     HIPCHK(c, hipMemsetAsync(head, 0, headb, st));
     HIPCHK(c, hipEventRecord(c->ev[0][0], st));
     /* chunks per wave: a lane's loop is a chain of dependent HBM round trips and a wave steps at the pace of its
@@ -502,25 +568,16 @@ static int deflate_lane_path(qzd_ctx *c, const uint8_t *d_src, uint64_t n, uint3
     uint32_t lpw = 1;
     if (const char *e = getenv("QATZIP_AMD_LANE_LPW")) { const uint32_t v = (uint32_t)atoi(e); if (v >= 1 && v <= 64 && !(v & (v - 1))) lpw = v; }
     hipLaunchKernelGGL(qzk_lz77_lane_kernel, dim3((nchunks + lpw - 1) / lpw), dim3(lpw), 0, st, d_src, n, chunk_sz, nchunks,
-                       sym_lc, sym_dist, meta, head, prev, qzk_level_cfg(level), cdesc);
+                       y.sym_lc, y.sym_dist, y.meta, head, prev, qzk_level_cfg(level), cdesc);
     HIPCHK(c, hipEventRecord(c->ev[0][1], st));
-    hipLaunchKernelGGL(qzk_huff_kernel, dim3(nchunks), dim3(QZK_HW), 0, st, d_src, n, chunk_sz, nchunks, sym_lc, sym_dist,
-                       meta, slots, stride, last ? nchunks - 1 : ~0u, c->d_len, cdesc);
-    hipLaunchKernelGGL(qzk_crc_chunks_kernel, dim3(nchunks), dim3(QZK_HT), 0, st, d_src, n, chunk_sz, nchunks, c->d_crc, cdesc);
+    launch_huff_crc(c, st, d_src, n, chunk_sz, nchunks, y, last ? nchunks - 1 : ~0u, 0, cdesc);
     HIPCHK(c, hipEventRecord(c->ev[0][2], st));
-    hipLaunchKernelGGL(qzk_scan_kernel, dim3(1), dim3(1024), 0, st, c->d_len, nchunks, c->d_offs, c->d_running);
-    hipLaunchKernelGGL(qzk_gather_kernel, dim3(nchunks), dim3(256), 0, st, slots, stride, c->d_len, c->d_offs, nchunks,
-                       d_dst, dst_cap, c->d_overflow);
+    launch_scan_gather(c, st, y.slots, slot_stride_for(chunk_sz), 0, nchunks, d_dst, dst_cap);
     HIPCHK(c, hipEventRecord(c->ev[0][3], st));
-    HIPCHK(c, hipMemcpyAsync(c->h_running, c->d_running, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(c->h_overflow, c->d_overflow, 4, hipMemcpyDeviceToHost, st));
+    QZD_TRY(publish_totals(c, st));
     HIPCHK(c, hipEventRecord(c->ev_end, st));
-    HIPCHK(c, hipGetLastError());
     return QZD_OK;
 }
-
-static int deflate_lazy_path(qzd_ctx *c, const uint8_t *d_src, uint64_t n, uint32_t chunk_sz, int level, int last,
-                             uint8_t *d_dst, uint64_t dst_cap, uint32_t nchunks, const uint32_t *cdesc);
 
 #include "qzk_deflate_wide.h"
 static uint64_t *g_wide_prof; static uint32_t g_wide_prof_cap, g_wide_prof_n;     /* QATZIP_AMD_WIDE_PROF=1: phase clocks of the last call */
@@ -530,35 +587,11 @@ static uint64_t *g_wide_prof; static uint32_t g_wide_prof_cap, g_wide_prof_n;   
 static int deflate_wide_path(qzd_ctx *c, const uint8_t *d_src, uint64_t n, uint32_t chunk_sz, int last,
                              uint8_t *d_dst, uint64_t dst_cap, uint32_t nchunks, const uint32_t *cdesc)
 {
-    const uint32_t stride = slot_stride_for(chunk_sz);
     const uint32_t wgs = nchunks < c->cus ? nchunks : c->cus;
-    const size_t symb = ((size_t)nchunks * chunk_sz + 511) & ~(size_t)255;
-    const size_t metab = ((size_t)nchunks * sizeof(qzk_lzmeta) + 255) & ~(size_t)255;
-    const size_t slotb = ((size_t)nchunks * stride + 255) & ~(size_t)255;
-    const size_t prevb = (size_t)wgs * 65536 * 2;
-    const size_t need = symb * 3 + metab + slotb + prevb + 256;
-    if (need > c->lane_cap) {
-        hipDeviceSynchronize();
-        if (c->d_lane) hipFree(c->d_lane);
-        c->d_lane = NULL; c->lane_cap = 0;
-        HIPCHK(c, hipMalloc(&c->d_lane, need));
-        c->lane_cap = need;
-    }
-    if (nchunks > c->call_cap) {
-        hipDeviceSynchronize();
-        hipFree(c->d_len); hipFree(c->d_crc); hipFree(c->d_offs);
-        c->d_len = NULL; c->d_crc = NULL; c->d_offs = NULL; c->call_cap = 0;
-        HIPCHK(c, hipMalloc(&c->d_len, (size_t)nchunks * 4));
-        HIPCHK(c, hipMalloc(&c->d_crc, (size_t)nchunks * 4));
-        HIPCHK(c, hipMalloc(&c->d_offs, QZD_OFFS_BYTES(nchunks)));
-        c->call_cap = nchunks;
-    }
-    uint8_t *pb = c->d_lane;
-    uint8_t *sym_lc = pb; pb += symb;
-    uint16_t *sym_dist = (uint16_t *)pb; pb += 2 * symb;
-    qzk_lzmeta *meta = (qzk_lzmeta *)pb; pb += metab;
-    uint8_t *slots = pb; pb += slotb;
-    uint16_t *prevtab = (uint16_t *)pb;
+    qzd_symbufs y; uint8_t *own;
+    QZD_TRY(carve_symbols(c, nchunks, chunk_sz, (size_t)wgs * 65536 * 2, &y, &own));
+    QZD_TRY(reserve_call_arrays(c, nchunks));
+    uint16_t *prevtab = (uint16_t *)own;
     uint64_t *xprof = NULL;
     if (const char *e = getenv("QATZIP_AMD_WIDE_PROF")) if (e[0] == '1') {
         if (nchunks > g_wide_prof_cap) { hipDeviceSynchronize(); if (g_wide_prof) hipFree(g_wide_prof); g_wide_prof = NULL; g_wide_prof_cap = 0;
@@ -566,129 +599,159 @@ static int deflate_wide_path(qzd_ctx *c, const uint8_t *d_src, uint64_t n, uint3
         if (g_wide_prof) { xprof = g_wide_prof; g_wide_prof_n = nchunks; hipMemsetAsync(xprof, 0, (size_t)nchunks * 128, c->st[0]); }
     }
     hipStream_t st = c->st[0];
-    c->last_nchunks = nchunks; c->nbatches = 1; c->k1ev_n = 0;
-    HIPCHK(c, hipMemsetAsync(c->d_running, 0, 8, st));
-    HIPCHK(c, hipMemsetAsync(c->d_overflow, 0, 4, st));
     HIPCHK(c, hipMemsetAsync(c->k1_counter, 0, 4, st));
-    HIPCHK(c, hipEventRecord(c->ev_begin, st));
+    QZD_TRY(call_begin(c, st, nchunks, 1));
     HIPCHK(c, hipEventRecord(c->ev[0][0], st));
     HIPCHK(c, hipEventRecord(c->k1ev[0][0], st));
-    hipLaunchKernelGGL(qzk_lz77_wide_kernel, dim3(wgs), dim3(QZX_W), 0, st, d_src, n, chunk_sz, nchunks, sym_lc, sym_dist, meta,
+    hipLaunchKernelGGL(qzk_lz77_wide_kernel, dim3(wgs), dim3(QZX_W), 0, st, d_src, n, chunk_sz, nchunks, y.sym_lc, y.sym_dist, y.meta,
                        prevtab, c->k1_counter, cdesc, xprof);
     HIPCHK(c, hipEventRecord(c->k1ev[0][1], st)); c->k1ev_chunks[0] = nchunks; c->k1ev_n = 1;
     HIPCHK(c, hipEventRecord(c->ev[0][1], st));
-    hipLaunchKernelGGL(qzk_huff_kernel, dim3(nchunks), dim3(QZK_HW), 0, st, d_src, n, chunk_sz, nchunks, sym_lc, sym_dist,
-                       meta, slots, stride, last ? nchunks - 1 : ~0u, c->d_len, cdesc);
-    hipLaunchKernelGGL(qzk_crc_chunks_kernel, dim3(nchunks), dim3(QZK_HT), 0, st, d_src, n, chunk_sz, nchunks, c->d_crc, cdesc);
+    launch_huff_crc(c, st, d_src, n, chunk_sz, nchunks, y, last ? nchunks - 1 : ~0u, 0, cdesc);
     HIPCHK(c, hipEventRecord(c->ev[0][2], st));
-    hipLaunchKernelGGL(qzk_scan_kernel, dim3(1), dim3(1024), 0, st, c->d_len, nchunks, c->d_offs, c->d_running);
-    hipLaunchKernelGGL(qzk_gather_kernel, dim3(nchunks), dim3(256), 0, st, slots, stride, c->d_len, c->d_offs, nchunks,
-                       d_dst, dst_cap, c->d_overflow);
+    launch_scan_gather(c, st, y.slots, slot_stride_for(chunk_sz), 0, nchunks, d_dst, dst_cap);
     HIPCHK(c, hipEventRecord(c->ev[0][3], st));
-    HIPCHK(c, hipMemcpyAsync(c->h_running, c->d_running, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(c->h_overflow, c->d_overflow, 4, hipMemcpyDeviceToHost, st));
+    QZD_TRY(publish_totals(c, st));
     HIPCHK(c, hipEventRecord(c->ev_end, st));
-    HIPCHK(c, hipGetLastError());
     return QZD_OK;
 }
 
-/* cdesc (device memory, or NULL): per-chunk length / closes-its-stream flag of a coalesced launch (qzk_chunk_len) */
-static int deflate_enqueue_impl(qzd_ctx *c, const uint8_t *d_src, uint64_t n, uint32_t chunk_sz, int level,
-                                int last, uint8_t *d_dst, uint64_t dst_cap, const uint32_t *cdesc, const uint8_t *h_src);
-static int deflate_enqueue(qzd_ctx *c, const uint8_t *d_src, uint64_t n, uint32_t chunk_sz, int level,
-                           int last, uint8_t *d_dst, uint64_t dst_cap, const uint32_t *cdesc, const uint8_t *h_src = NULL)
-{
-    return deflate_enqueue_impl(c, d_src, n, chunk_sz, level, last, d_dst, dst_cap, cdesc, h_src);
-}
-static int deflate_enqueue_impl(qzd_ctx *c, const uint8_t *d_src, uint64_t n, uint32_t chunk_sz, int level,
-                                int last, uint8_t *d_dst, uint64_t dst_cap, const uint32_t *cdesc, const uint8_t *h_src)
-{
-    if (!c || !d_dst || (n && !d_src)) return QZD_ERR_PARAM;
-    if (chunk_sz < 1024 || chunk_sz > 512 * 1024 || (chunk_sz & (chunk_sz - 1))) return QZD_ERR_PARAM;
-    if (level < 1 || level > 9) { snprintf(c->err, sizeof(c->err), "deflate level %d: zlib has levels 1-9", level); return QZD_ERR_UNSUPPORTED; }
-    if (n > ((uint64_t)1 << 32)) return QZD_ERR_PARAM;
-    hipSetDevice(c->device);
-    const uint32_t nchunks = n ? (uint32_t)((n + chunk_sz - 1) / chunk_sz) : 1;
+/* ------------------------------------------------------------------ level 1, a call that fills the chip (K1) */
+/* The device's tables and batch scratch are used by one call at a time - on the GPU: this call's streams wait for the
+ * event the previous call (of whichever context) recorded behind its last launch, and leave theirs when everything is
+ * enqueued.  The mutex is held while deflate_k1_path runs and never across API calls. */
+struct PoolGuard {
+    qzd_k1pool *p; qzd_ctx *c; bool launched;
+    PoolGuard(qzd_k1pool *p_, qzd_ctx *c_) : p(p_), c(c_), launched(false) { pthread_mutex_lock(&p->lock); }
+    ~PoolGuard()
     {
-        /* level 1: one chunk per wave (K1, window speculation over the four-newest table); levels 2-9: zlib's own loop
-         * and tables, one chunk per LANE (K1b).  QATZIP_AMD_DEFLATE=lane takes level 1 through K1b as well. */
-        const char *force = getenv("QATZIP_AMD_DEFLATE");
-        if ((level != 1 || (force && force[0] == 'l')) && h_src && n) { HIPCHK(c, hipMemcpyAsync((void *)d_src, h_src, n, hipMemcpyHostToDevice, c->st[0])); HIPCHK(c, hipStreamSynchronize(c->st[0])); }    /* (not the null stream: it would wait for every blocking stream of the process) */
-        /* the lazy levels have their own, parallel, path; QATZIP_AMD_LAZY=0 sends them through K1b instead */
-        const char *lz = getenv("QATZIP_AMD_LAZY");
-        if (level >= 4 && !(lz && lz[0] == '0')) return deflate_lazy_path(c, d_src, n, chunk_sz, level, last, d_dst, dst_cap, nchunks, cdesc);
-        if (level != 1 || (force && force[0] == 'l')) return deflate_lane_path(c, d_src, n, chunk_sz, level, last, d_dst, dst_cap, nchunks, cdesc);
-        /* Two parse kernels for level 1.  A call that fills the chip gives every wave a chunk of its own (K1,
-         * qzk_lz77_pull_kernel: 4096 chunks in flight hide each other's latency; throughput).  A launch of at most one chunk
-         * per CU - a lone qzCompress of a block or two, the requests a few threads have in flight - gives every chunk a
-         * whole CU instead (K1w, qzk_lz77_wide_kernel: the chunk, prev[] and the window's work on chip; latency: a chunk
-         * takes about half the time one wave needs).  QATZIP_AMD_K1=wide / pull forces one of them. */
-        const char *k1 = getenv("QATZIP_AMD_K1");
-        const bool force_wide = k1 && k1[0] == 'w', force_pull = k1 && k1[0] == 'p';
-        if (chunk_sz <= 65536 && (force_wide || (!force_pull && nchunks <= c->cus + c->cus / 2))) {      /* measured crossover: profiles/r4_k1_crossover.txt */
-            if (h_src && n) { HIPCHK(c, hipMemcpyAsync((void *)d_src, h_src, n, hipMemcpyHostToDevice, c->st[0])); HIPCHK(c, hipStreamSynchronize(c->st[0])); }
-            return deflate_wide_path(c, d_src, n, chunk_sz, last, d_dst, dst_cap, nchunks, cdesc);
+        if (launched) {
+            /* behind everything this call put on its streams (st[1] and the copy stream are joined into st[0] on the
+             * success path; on an error path both are waited for here) */
+            if (!p->busy) hipEventCreateWithFlags(&p->busy, hipEventDisableTiming);
+            hipEvent_t j = c->done[1];
+            if (hipEventRecord(j, c->st[1]) == hipSuccess) hipStreamWaitEvent(c->st[0], j, 0);
+            if (p->busy && hipEventRecord(p->busy, c->st[0]) == hipSuccess) p->busy_valid = true;
+            else { hipStreamSynchronize(c->st[0]); hipStreamSynchronize(c->st[1]); p->busy_valid = false; }
+        }
+        pthread_mutex_unlock(&p->lock);
+    }
+};
+
+/* a launch that waits for its input must hear from the host on every way out of deflate_k1_path: whatever returns
+ * early (a HIP error between the launch and the copy) leaves the watermark at "giving up" */
+struct FedGuard {
+    uint32_t *wm; bool armed;
+    ~FedGuard() { if (armed && wm) __atomic_store_n(&wm[0], 0xffffffffu, __ATOMIC_RELEASE); }
+};
+
+/* the device's tables and batch scratch for a call of nchunks chunks: taken for the whole call (released by qzd_sync, or
+ * by the caller of deflate_enqueue when it fails).  Called with the pool's lock held. */
+static int k1_pool_acquire(qzd_ctx *c, qzd_k1pool *pool, uint32_t chunk_sz, uint32_t nchunks)
+{
+    const uint32_t max_wgs = (c->k1_wgs + QZK_K1_WAVES - 1) / QZK_K1_WAVES;      /* workgroups of a full launch (QZK_K1_OCC per CU) */
+    /* a launch of few chunks spreads them over workgroups (CUs) before it stacks them on the waves of one */
+    const uint32_t want = nchunks < max_wgs ? nchunks : max_wgs;
+    QZD_TRY(ensure_scratch(c, pool, chunk_sz, nchunks));
+    if (want > pool->tab_wgs) {
+        hipDeviceSynchronize();
+        if (pool->tables) hipFree(pool->tables);
+        pool->tables = NULL; pool->tab_wgs = 0;
+        const uint32_t get = want > max_wgs / 4 ? max_wgs : want;     /* a big call: take the whole set at once */
+        const size_t tb = (size_t)QZK_K1_TABROWS(get) * QZK_HSIZE * QZK_K1_TABW * sizeof(qzk_bkt);
+        if (hipMalloc(&pool->tables, tb) != hipSuccess || hipMemset(pool->tables, 0, tb) != hipSuccess ||   /* epoch 0 = never valid */
+            hipDeviceSynchronize() != hipSuccess) {                   /* hipMemset of device memory returns early, and the
+                                                                       * (non-blocking) work streams do not wait for it */
+            if (pool->tables) hipFree(pool->tables);
+            pool->tables = NULL;
+            snprintf(c->err, sizeof(c->err), "K1 tables: out of device memory");
+            return QZD_ERR_HIP;
+        }
+        pool->tab_wgs = get;
+    }
+    if ((uint64_t)pool->epoch + nchunks + 1 >= 0xffffffffull) {        /* epochs wrapped: forget everything once */
+        hipDeviceSynchronize();
+        hipMemset(pool->tables, 0, (size_t)QZK_K1_TABROWS(pool->tab_wgs) * QZK_HSIZE * QZK_K1_TABW * sizeof(qzk_bkt));
+        hipDeviceSynchronize();
+        pool->epoch = 1;
+    }
+    return QZD_OK;
+}
+
+/* Host input of 64 MiB and more (level 1, chunks of the common kind): ONE launch over the whole call that starts at
+ * once and takes its chunks as they land - the pieces of the copy go out behind it and the host raises the launch's
+ * watermark (c->h_wm, pinned) as each completes (qzk_wait_input).  No batch boundaries, so no tails but the last one,
+ * and the parse runs beside the whole copy instead of beside all but the first batch of it.
+ * The launch fills every register file and then WAITS for the copy: that is only safe when the copy needs none of the
+ * compute units and cannot stall behind the host - page-locked source memory moved by a copy engine.  A pageable
+ * source (staged by the runtime piece by piece), a source that is not the caller's pinned memory, or a process that
+ * has switched the copy engines off (HSA_ENABLE_SDMA=0: copies become kernels, which cannot run beside the resident
+ * waves) take the batched pipeline; so does the retry of a call whose launch gave up waiting (c->no_stream_in,
+ * qzd_deflate_raw_from_host). */
+static bool k1_stream_in_ok(qzd_ctx *c, const uint8_t *h_src, uint64_t n, bool fuse, const uint32_t *cdesc)
+{
+    if (!(h_src && fuse && !cdesc && n >= (64ull << 20) && c->h_wm && !c->no_stream_in && !getenv("QATZIP_AMD_HOST_BATCHED"))) return false;
+    const char *sd = getenv("HSA_ENABLE_SDMA");
+    if (sd && sd[0] == '0') return false;
+    hipPointerAttribute_t a0, a1;
+    const bool p0 = hipPointerGetAttributes(&a0, h_src) == hipSuccess && a0.type == hipMemoryTypeHost;
+    const bool p1 = p0 && hipPointerGetAttributes(&a1, h_src + n - 1) == hipSuccess && a1.type == hipMemoryTypeHost;
+    if (!p1) (void)hipGetLastError();     /* (an unregistered pointer is an error to the query: cleared) */
+    return p1;
+}
+
+/* the copy behind a fed launch, in pieces (small ones first: the launch is waiting), two in flight; the watermark follows
+ * the last piece known to be complete.  Whatever goes wrong, the launch is told (0xffffffff) before this returns. */
+static int k1_feed_host_input(qzd_ctx *c, const uint8_t *d_src, const uint8_t *h_src, uint64_t n, uint32_t chunk_sz, uint32_t nchunks)
+{
+    uint64_t off = 0, ends[QZD_NBUF + 1] = {0};
+    hipError_t e = hipSuccess;
+    uint32_t i = 0;
+    const bool trace = getenv("QATZIP_AMD_STREAM_TRACE") != NULL;
+    struct timespec ts0; clock_gettime(CLOCK_MONOTONIC, &ts0);
+    auto landed = [&](uint64_t upto) {
+        __atomic_store_n(&c->h_wm[0], upto >= n ? nchunks : (uint32_t)(upto / chunk_sz), __ATOMIC_RELEASE);
+        if (trace) {
+            struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t);
+            fprintf(stderr, "[stream] %8.3f ms  %6.1f MiB landed\n", (t.tv_sec - ts0.tv_sec) * 1e3 + (t.tv_nsec - ts0.tv_nsec) / 1e6, upto / 1048576.0);
+        }
+    };
+    for (; off < n && e == hipSuccess; i++) {
+        /* every wave of the launch has pulled a chunk and waits for it: fine steps while they start (the first
+         * 256 MiB feed the first chunk of each of 4096 waves), coarse ones once the copy is ahead of the parse */
+        const uint64_t want = i < 2 ? (4ull << 20) : off < (256ull << 20) ? (8ull << 20) : (64ull << 20);
+        const uint64_t len = std::min<uint64_t>(want, n - off);
+        e = hipMemcpyAsync((void *)(d_src + off), h_src + off, len, hipMemcpyHostToDevice, c->st_copy);
+        if (e == hipSuccess) e = hipEventRecord(c->cp_ev[i % (QZD_NBUF + 1)], c->st_copy);
+        off += len; ends[i % (QZD_NBUF + 1)] = off;
+        if (i >= 1 && e == hipSuccess) {
+            e = hipEventSynchronize(c->cp_ev[(i - 1) % (QZD_NBUF + 1)]);
+            if (e == hipSuccess) landed(ends[(i - 1) % (QZD_NBUF + 1)]);
         }
     }
-    const uint32_t max_wgs = (c->k1_wgs + QZK_K1_WAVES - 1) / QZK_K1_WAVES;      /* workgroups of a full launch (QZK_K1_OCC per CU) */
+    if (e == hipSuccess && i) e = hipEventSynchronize(c->cp_ev[(i - 1) % (QZD_NBUF + 1)]);
+    if (e != hipSuccess) {
+        __atomic_store_n(&c->h_wm[0], 0xffffffffu, __ATOMIC_RELEASE);
+        HIPCHK(c, e);
+    }
+    landed(n);
+    return QZD_OK;
+}
+
+/* K1 (qzk_lz77_pull_kernel) with K2 and the chunk CRCs in its waves, or behind it with QATZIP_AMD_FUSE=0; batches
+ * alternate over the two streams, and st[0] publishes the totals behind both */
+static int deflate_k1_path(qzd_ctx *c, const uint8_t *d_src, uint64_t n, uint32_t chunk_sz, int last, uint8_t *d_dst,
+                           uint64_t dst_cap, uint32_t nchunks, const uint32_t *cdesc, const uint8_t *h_src)
+{
     qzd_k1pool *const pool = &g_k1pool[c->device % QZD_MAX_DEVICES];
     pthread_once(&g_k1pool_once, k1pool_init);
-    /* The device's tables and batch scratch are used by one call at a time - on the GPU: this call's streams wait for the
-     * event the previous call (of whichever context) recorded behind its last launch, and leave theirs when everything is
-     * enqueued.  The mutex is held while this function runs and never across API calls. */
-    struct PoolGuard {
-        qzd_k1pool *p; qzd_ctx *c; bool launched;
-        PoolGuard(qzd_k1pool *p_, qzd_ctx *c_) : p(p_), c(c_), launched(false) { pthread_mutex_lock(&p->lock); }
-        ~PoolGuard()
-        {
-            if (launched) {
-                /* behind everything this call put on its streams (st[1] and the copy stream are joined into st[0] on the
-                 * success path; on an error path both are waited for here) */
-                if (!p->busy) hipEventCreateWithFlags(&p->busy, hipEventDisableTiming);
-                hipEvent_t j = c->done[1];
-                if (hipEventRecord(j, c->st[1]) == hipSuccess) hipStreamWaitEvent(c->st[0], j, 0);
-                if (p->busy && hipEventRecord(p->busy, c->st[0]) == hipSuccess) p->busy_valid = true;
-                else { hipStreamSynchronize(c->st[0]); hipStreamSynchronize(c->st[1]); p->busy_valid = false; }
-            }
-            pthread_mutex_unlock(&p->lock);
-        }
-    } guard(pool, c);
+    PoolGuard guard(pool, c);
     if (pool->busy_valid) {
         HIPCHK(c, hipStreamWaitEvent(c->st[0], pool->busy, 0));
         HIPCHK(c, hipStreamWaitEvent(c->st[1], pool->busy, 0));
     }
-    {
-        /* a launch of few chunks spreads them over workgroups (CUs) before it stacks them on the waves of one */
-        const uint32_t want = nchunks < max_wgs ? nchunks : max_wgs;
-        /* the device's tables and batch scratch: taken for the whole call (released by qzd_sync, or by the caller of
-         * this function when it fails) */
-        const int rc = ensure_scratch(c, pool, chunk_sz, nchunks);
-        if (rc) return rc;
-        if (want > pool->tab_wgs) {
-            hipDeviceSynchronize();
-            if (pool->tables) hipFree(pool->tables);
-            pool->tables = NULL; pool->tab_wgs = 0;
-            const uint32_t get = want > max_wgs / 4 ? max_wgs : want;     /* a big call: take the whole set at once */
-            const size_t tb = (size_t)QZK_K1_TABROWS(get) * QZK_HSIZE * QZK_K1_TABW * sizeof(qzk_bkt);
-            if (hipMalloc(&pool->tables, tb) != hipSuccess || hipMemset(pool->tables, 0, tb) != hipSuccess ||   /* epoch 0 = never valid */
-                hipDeviceSynchronize() != hipSuccess) {                   /* hipMemset of device memory returns early, and the
-                                                                           * (non-blocking) work streams do not wait for it */
-                if (pool->tables) hipFree(pool->tables);
-                pool->tables = NULL;
-                snprintf(c->err, sizeof(c->err), "K1 tables: out of device memory");
-                return QZD_ERR_HIP;
-            }
-            pool->tab_wgs = get;
-        }
-        if ((uint64_t)pool->epoch + nchunks + 1 >= 0xffffffffull) {        /* epochs wrapped: forget everything once */
-            hipDeviceSynchronize();
-            hipMemset(pool->tables, 0, (size_t)QZK_K1_TABROWS(pool->tab_wgs) * QZK_HSIZE * QZK_K1_TABW * sizeof(qzk_bkt));
-            hipDeviceSynchronize();
-            pool->epoch = 1;
-        }
-    }
+    QZD_TRY(k1_pool_acquire(c, pool, chunk_sz, nchunks));
     const uint32_t stride = slot_stride_for(chunk_sz);
-    c->last_nchunks = nchunks;
     /* input already in HBM and K2 inside K1: the whole call is ONE launch - every launch ends with a tail (the waves
      * finish their last chunks, ~8 ms each, at different times; on the bench data ~3 ms of a 12288-chunk launch) and there
      * is nothing left to overlap it with.  Input still on the host: batches, so that the copy of the next one runs beside
@@ -700,34 +763,9 @@ static int deflate_enqueue_impl(qzd_ctx *c, const uint8_t *d_src, uint64_t n, ui
         if (const char *e = getenv("QATZIP_AMD_HOST_BATCH")) { const uint32_t v = (uint32_t)atoi(e); if (v >= 256) BATCH = v; }
         if (const char *e = getenv("QATZIP_AMD_HOST_FIRST")) { const uint32_t v = (uint32_t)atoi(e); if (v >= 256) first_env = v; }
     }
-    /* Host input of 64 MiB and more (level 1, chunks of the common kind): ONE launch over the whole call that starts at
-     * once and takes its chunks as they land - the pieces of the copy go out behind it and the host raises the launch's
-     * watermark (c->h_wm, pinned) as each completes (qzk_wait_input).  No batch boundaries, so no tails but the last one,
-     * and the parse runs beside the whole copy instead of beside all but the first batch of it. */
-    /* The launch fills every register file and then WAITS for the copy: that is only safe when the copy needs none of the
-     * compute units and cannot stall behind the host - page-locked source memory moved by a copy engine.  A pageable
-     * source (staged by the runtime piece by piece), a source that is not the caller's pinned memory, or a process that
-     * has switched the copy engines off (HSA_ENABLE_SDMA=0: copies become kernels, which cannot run beside the resident
-     * waves) take the batched pipeline; so does the retry of a call whose launch gave up waiting (c->no_stream_in,
-     * qzd_deflate_raw_from_host). */
-    bool stream_in = h_src && fuse && !cdesc && n >= (64ull << 20) && c->h_wm && !c->no_stream_in && !getenv("QATZIP_AMD_HOST_BATCHED");
-    if (stream_in) {
-        const char *sd = getenv("HSA_ENABLE_SDMA");
-        if (sd && sd[0] == '0') stream_in = false;
-    }
-    if (stream_in) {
-        hipPointerAttribute_t a0, a1;
-        const bool p0 = hipPointerGetAttributes(&a0, h_src) == hipSuccess && a0.type == hipMemoryTypeHost;
-        const bool p1 = p0 && hipPointerGetAttributes(&a1, h_src + n - 1) == hipSuccess && a1.type == hipMemoryTypeHost;
-        if (!p1) { (void)hipGetLastError(); stream_in = false; }     /* (an unregistered pointer is an error to the query: cleared) */
-    }
+    const bool stream_in = k1_stream_in_ok(c, h_src, n, fuse, cdesc);
     if (stream_in) { BATCH = nchunks; first_env = 0; c->h_wm[0] = 0; c->h_wm[1] = 0; }
-    /* a launch that waits for its input must hear from the host on every way out of this function: whatever returns
-     * early (a HIP error between the launch and the copy) leaves the watermark at "giving up" */
-    struct FedGuard {
-        uint32_t *wm; bool armed;
-        ~FedGuard() { if (armed && wm) __atomic_store_n(&wm[0], 0xffffffffu, __ATOMIC_RELEASE); }
-    } fed_guard = { c->h_wm, stream_in };
+    FedGuard fed_guard = { c->h_wm, stream_in };
     /* one launch for the whole call: its waves also move the stream to d_dst (qzk_outp) - no scan, no gather behind it */
     const char *oute = getenv("QATZIP_AMD_K1_OUT");
     /* (measured, profiles/r3_api_stream.txt: with the destination across PCIe the stream then travels while the parse runs,
@@ -742,13 +780,8 @@ static int deflate_enqueue_impl(qzd_ctx *c, const uint8_t *d_src, uint64_t n, ui
         outp.pub = (uint32_t *)(c->d_offs + nchunks + 1); outp.running = c->d_running; outp.overflow = c->d_overflow;
         HIPCHK(c, hipMemsetAsync(c->d_offs, 0, QZD_OFFS_BYTES(nchunks), c->st[0]));
     }
-    c->k1ev_n = 0;
-    c->nbatches = (nchunks + BATCH - 1) / BATCH;
-
     guard.launched = true;
-    HIPCHK(c, hipMemsetAsync(c->d_running, 0, 8, c->st[0]));
-    HIPCHK(c, hipMemsetAsync(c->d_overflow, 0, 4, c->st[0]));
-    HIPCHK(c, hipEventRecord(c->ev_begin, c->st[0]));
+    QZD_TRY(call_begin(c, c->st[0], nchunks, (nchunks + BATCH - 1) / BATCH));
     HIPCHK(c, hipEventRecord(c->done[0], c->st[0]));
     HIPCHK(c, hipStreamWaitEvent(c->st[1], c->done[0], 0));
 
@@ -765,6 +798,7 @@ static int deflate_enqueue_impl(qzd_ctx *c, const uint8_t *d_src, uint64_t n, ui
         const uint64_t boff = (uint64_t)b * chunk_sz;
         const uint64_t blen = n - boff;      /* bytes from this batch's first chunk to the end of the call */
         const uint32_t final_chunk = (last && b + bn == nchunks) ? bn - 1 : ~0u;
+        const uint32_t *const cd = cdesc ? cdesc + b : NULL;
         hipStream_t st = c->st[s];
         const bool timed = k < QZD_NBUF;     /* events of the first use of each buffer set */
         /* input still in host memory: batch k's bytes were sent while batch k-1 was enqueued (below); its kernels wait
@@ -790,38 +824,24 @@ static int deflate_enqueue_impl(qzd_ctx *c, const uint8_t *d_src, uint64_t n, ui
         if (timed) HIPCHK(c, hipEventRecord(c->ev[s][0], st));
         if (k < QZD_K1EV) HIPCHK(c, hipEventRecord(c->k1ev[k][0], st));
         /* K2 rides in the K1 waves (qzk_lz77_pull_kernel): symbols per wave, slots / meta by the chunk's number in the call */
-        uint8_t *const slots_b = fuse ? pool->slots[0] + (size_t)b * stride : pool->slots[s];
-        qzk_lzmeta *const meta_b = fuse ? pool->meta[0] + b : pool->meta[s];
         const int sb = fuse ? 0 : s;
-        if (stream_in || out_in_launch)
-            hipLaunchKernelGGL(qzk_lz77_pull_fed_kernel, dim3(wgs), dim3(64 * wpw), 0, st, d_src + boff, blen, chunk_sz, bn,
-                               pool->sym_lc[sb], pool->sym_dist[sb], meta_b, pool->tables, c->k1_counter + s, cdesc ? cdesc + b : NULL,
-                               pool->epoch, fuse ? slots_b : (uint8_t *)NULL, stride, final_chunk, c->d_len + b,
-                               fuse ? c->d_crc + b : (uint32_t *)NULL, stream_in ? (const uint32_t *)c->h_wm : (const uint32_t *)NULL, outp);
-        else
-            hipLaunchKernelGGL(qzk_lz77_pull_kernel, dim3(wgs), dim3(64 * wpw), 0, st, d_src + boff, blen, chunk_sz, bn,
-                               pool->sym_lc[sb], pool->sym_dist[sb], meta_b, pool->tables, c->k1_counter + s, cdesc ? cdesc + b : NULL,
-                               pool->epoch, fuse ? slots_b : (uint8_t *)NULL, stride, final_chunk, c->d_len + b,
-                               fuse ? c->d_crc + b : (uint32_t *)NULL, (const uint32_t *)NULL, outp);
+        const qzd_symbufs y = { pool->sym_lc[sb], pool->sym_dist[sb], fuse ? pool->meta[0] + b : pool->meta[s],
+                                fuse ? pool->slots[0] + (size_t)b * stride : pool->slots[s] };
+        /* the kernel that can wait for its input and move its output only where a call needs either */
+        const auto k1 = stream_in || out_in_launch ? qzk_lz77_pull_fed_kernel : qzk_lz77_pull_kernel;
+        hipLaunchKernelGGL(k1, dim3(wgs), dim3(64 * wpw), 0, st, d_src + boff, blen, chunk_sz, bn, y.sym_lc, y.sym_dist, y.meta,
+                           pool->tables, c->k1_counter + s, cd, pool->epoch, fuse ? y.slots : (uint8_t *)NULL, stride, final_chunk,
+                           c->d_len + b, fuse ? c->d_crc + b : (uint32_t *)NULL,
+                           stream_in ? (const uint32_t *)c->h_wm : (const uint32_t *)NULL, outp);
         pool->epoch += bn;
         HIPCHK(c, hipEventRecord(c->k1done[s], st));
         if (k < QZD_K1EV) { HIPCHK(c, hipEventRecord(c->k1ev[k][1], st)); c->k1ev_chunks[k] = bn; c->k1ev_n = k + 1; }
         if (timed) HIPCHK(c, hipEventRecord(c->ev[s][1], st));
-        if (!fuse)
-            hipLaunchKernelGGL(qzk_huff_kernel, dim3(bn), dim3(QZK_HW), 0, st, d_src + boff, blen, chunk_sz, bn,
-                               pool->sym_lc[s], pool->sym_dist[s], pool->meta[s], pool->slots[s], stride, final_chunk,
-                               c->d_len + b, cdesc ? cdesc + b : NULL);
-        if (!fuse)          /* fused: the chunk CRCs ride along K1's input reads */
-            hipLaunchKernelGGL(qzk_crc_chunks_kernel, dim3(bn), dim3(QZK_HT), 0, st, d_src + boff, blen, chunk_sz, bn, c->d_crc + b,
-                               cdesc ? cdesc + b : NULL);
+        if (!fuse) launch_huff_crc(c, st, d_src + boff, blen, chunk_sz, bn, y, final_chunk, b, cd);    /* fused: the chunk CRCs ride along K1's input reads */
         if (timed) HIPCHK(c, hipEventRecord(c->ev[s][2], st));
         /* the running total serialises scan/gather of consecutive batches across the two streams */
         if (k > 0) HIPCHK(c, hipStreamWaitEvent(st, c->done[so], 0));
-        if (!out_in_launch) {
-            hipLaunchKernelGGL(qzk_scan_kernel, dim3(1), dim3(1024), 0, st, c->d_len + b, bn, c->d_offs + b, c->d_running);
-            hipLaunchKernelGGL(qzk_gather_kernel, dim3(bn), dim3(256), 0, st, slots_b, stride, c->d_len + b,
-                               c->d_offs + b, bn, d_dst, dst_cap, c->d_overflow);
-        }
+        if (!out_in_launch) launch_scan_gather(c, st, y.slots, stride, b, bn, d_dst, dst_cap);
         if (timed) HIPCHK(c, hipEventRecord(c->ev[s][3], st));
         HIPCHK(c, hipEventRecord(c->done[s], st));
         if (h_src && !stream_in && bnext < nchunks) HIPCHK(c, send(k + 1, bnext));
@@ -829,46 +849,9 @@ static int deflate_enqueue_impl(qzd_ctx *c, const uint8_t *d_src, uint64_t n, ui
     /* join: stream 0 waits for stream 1, then publishes the totals */
     HIPCHK(c, hipStreamWaitEvent(c->st[0], c->done[1], 0));
     HIPCHK(c, hipStreamWaitEvent(c->st[0], c->done[0], 0));
-    HIPCHK(c, hipMemcpyAsync(c->h_running, c->d_running, 8, hipMemcpyDeviceToHost, c->st[0]));
-    HIPCHK(c, hipMemcpyAsync(c->h_overflow, c->d_overflow, 4, hipMemcpyDeviceToHost, c->st[0]));
+    QZD_TRY(publish_totals(c, c->st[0]));
     HIPCHK(c, hipEventRecord(c->ev_end, c->st[0]));
-    HIPCHK(c, hipGetLastError());
-    if (stream_in) {
-        /* the copy, in pieces (small ones first: the launch is waiting), two in flight; the watermark follows the last
-         * piece known to be complete.  Whatever goes wrong, the launch is told (0xffffffff) before this returns. */
-        uint64_t off = 0, done_to = 0, ends[QZD_NBUF + 1] = {0};
-        hipError_t e = hipSuccess;
-        uint32_t i = 0;
-        const bool trace = getenv("QATZIP_AMD_STREAM_TRACE") != NULL;
-        struct timespec ts0; clock_gettime(CLOCK_MONOTONIC, &ts0);
-        auto landed = [&](uint64_t upto) {
-            __atomic_store_n(&c->h_wm[0], upto >= n ? nchunks : (uint32_t)(upto / chunk_sz), __ATOMIC_RELEASE);
-            if (trace) {
-                struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t);
-                fprintf(stderr, "[stream] %8.3f ms  %6.1f MiB landed\n", (t.tv_sec - ts0.tv_sec) * 1e3 + (t.tv_nsec - ts0.tv_nsec) / 1e6, upto / 1048576.0);
-            }
-        };
-        for (; off < n && e == hipSuccess; i++) {
-            /* every wave of the launch has pulled a chunk and waits for it: fine steps while they start (the first
-             * 256 MiB feed the first chunk of each of 4096 waves), coarse ones once the copy is ahead of the parse */
-            const uint64_t want = i < 2 ? (4ull << 20) : off < (256ull << 20) ? (8ull << 20) : (64ull << 20);
-            const uint64_t len = std::min<uint64_t>(want, n - off);
-            e = hipMemcpyAsync((void *)(d_src + off), h_src + off, len, hipMemcpyHostToDevice, c->st_copy);
-            if (e == hipSuccess) e = hipEventRecord(c->cp_ev[i % (QZD_NBUF + 1)], c->st_copy);
-            off += len; ends[i % (QZD_NBUF + 1)] = off;
-            if (i >= 1 && e == hipSuccess) {
-                e = hipEventSynchronize(c->cp_ev[(i - 1) % (QZD_NBUF + 1)]);
-                if (e == hipSuccess) landed(done_to = ends[(i - 1) % (QZD_NBUF + 1)]);
-            }
-        }
-        if (e == hipSuccess && i) e = hipEventSynchronize(c->cp_ev[(i - 1) % (QZD_NBUF + 1)]);
-        if (e != hipSuccess) {
-            __atomic_store_n(&c->h_wm[0], 0xffffffffu, __ATOMIC_RELEASE);
-            HIPCHK(c, e);
-        }
-        landed(n);
-        (void)done_to;
-    }
+    if (stream_in) QZD_TRY(k1_feed_host_input(c, d_src, h_src, n, chunk_sz, nchunks));
     fed_guard.armed = false;
     return QZD_OK;
 }
@@ -881,44 +864,18 @@ static int deflate_enqueue_impl(qzd_ctx *c, const uint8_t *d_src, uint64_t n, ui
 static int deflate_lazy_path(qzd_ctx *c, const uint8_t *d_src, uint64_t n, uint32_t chunk_sz, int level, int last,
                              uint8_t *d_dst, uint64_t dst_cap, uint32_t nchunks, const uint32_t *cdesc)
 {
-    const uint32_t stride = slot_stride_for(chunk_sz);
     const uint32_t B = nchunks < QZD_LAZY_BATCH ? nchunks : QZD_LAZY_BATCH;
-    const size_t span = (size_t)B * chunk_sz;
-    const size_t symb = (span + 511) & ~(size_t)255;
-    const size_t metab = ((size_t)B * sizeof(qzk_lzmeta) + 255) & ~(size_t)255;
-    const size_t slotb = ((size_t)B * stride + 255) & ~(size_t)255;
+    const size_t symb = sym_bytes(B, chunk_sz);
     const size_t headb = (size_t)B * QZK_HSIZE * 4, pdb = 16 * symb, resb = 8 * symb;
-    const size_t need = symb * 3 + metab + slotb + headb + pdb + resb;
-    if (need > c->lane_cap) {
-        hipDeviceSynchronize();
-        if (c->d_lane) hipFree(c->d_lane);
-        c->d_lane = NULL; c->lane_cap = 0;
-        HIPCHK(c, hipMalloc(&c->d_lane, need));
-        c->lane_cap = need;
-    }
-    if (nchunks > c->call_cap) {
-        hipDeviceSynchronize();
-        hipFree(c->d_len); hipFree(c->d_crc); hipFree(c->d_offs);
-        c->d_len = NULL; c->d_crc = NULL; c->d_offs = NULL; c->call_cap = 0;
-        HIPCHK(c, hipMalloc(&c->d_len, (size_t)nchunks * 4));
-        HIPCHK(c, hipMalloc(&c->d_crc, (size_t)nchunks * 4));
-        HIPCHK(c, hipMalloc(&c->d_offs, QZD_OFFS_BYTES(nchunks)));
-        c->call_cap = nchunks;
-    }
-    uint8_t *pb = c->d_lane;
-    uint8_t *sym_lc = pb; pb += symb;
-    uint16_t *sym_dist = (uint16_t *)pb; pb += 2 * symb;
-    qzk_lzmeta *meta = (qzk_lzmeta *)pb; pb += metab;
-    uint8_t *slots = pb; pb += slotb;
-    uint32_t *head = (uint32_t *)pb; pb += headb;
-    qzk_lazyrec *pd = (qzk_lazyrec *)pb; pb += pdb;
-    qzk_lazyres *res = (qzk_lazyres *)pb;
+    qzd_symbufs y; uint8_t *own;
+    QZD_TRY(carve_symbols(c, B, chunk_sz, headb + pdb + resb, &y, &own));
+    QZD_TRY(reserve_call_arrays(c, nchunks));
+    uint32_t *head = (uint32_t *)own;
+    qzk_lazyrec *pd = (qzk_lazyrec *)(own + headb);
+    qzk_lazyres *res = (qzk_lazyres *)(own + headb + pdb);
     hipStream_t st = c->st[0];
     const qzk_lvlcfg cfg = qzk_level_cfg(level);
-    c->last_nchunks = nchunks; c->nbatches = 1;
-    HIPCHK(c, hipMemsetAsync(c->d_running, 0, 8, st));
-    HIPCHK(c, hipMemsetAsync(c->d_overflow, 0, 4, st));
-    HIPCHK(c, hipEventRecord(c->ev_begin, st));
+    QZD_TRY(call_begin(c, st, nchunks, 1));
     HIPCHK(c, hipEventRecord(c->ev[0][0], st));
     for (uint32_t b = 0; b < nchunks; b += B) {
         const uint32_t bn = nchunks - b < B ? nchunks - b : B;
@@ -929,22 +886,50 @@ static int deflate_lazy_path(qzd_ctx *c, const uint8_t *d_src, uint64_t n, uint3
         hipLaunchKernelGGL(qzk_lazy_chain_kernel, dim3(bn), dim3(64), 0, st, d_src + boff, blen, chunk_sz, bn, cd, head, pd);
         hipLaunchKernelGGL(qzk_lazy_search_kernel, dim3(bn), dim3(64), 0, st, d_src + boff, blen, chunk_sz, bn, cd, pd, res, cfg);
         hipLaunchKernelGGL(qzk_lazy_parse_kernel, dim3(bn), dim3(64), 0, st, d_src + boff, blen, chunk_sz, bn, cd, res,
-                           sym_lc, sym_dist, meta, cfg);
-        hipLaunchKernelGGL(qzk_huff_kernel, dim3(bn), dim3(QZK_HW), 0, st, d_src + boff, blen, chunk_sz, bn, sym_lc, sym_dist,
-                           meta, slots, stride, final_chunk, c->d_len + b, cd);
-        hipLaunchKernelGGL(qzk_crc_chunks_kernel, dim3(bn), dim3(QZK_HT), 0, st, d_src + boff, blen, chunk_sz, bn, c->d_crc + b, cd);
-        hipLaunchKernelGGL(qzk_scan_kernel, dim3(1), dim3(1024), 0, st, c->d_len + b, bn, c->d_offs + b, c->d_running);
-        hipLaunchKernelGGL(qzk_gather_kernel, dim3(bn), dim3(256), 0, st, slots, stride, c->d_len + b, c->d_offs + b, bn,
-                           d_dst, dst_cap, c->d_overflow);
+                           y.sym_lc, y.sym_dist, y.meta, cfg);
+        launch_huff_crc(c, st, d_src + boff, blen, chunk_sz, bn, y, final_chunk, b, cd);
+        launch_scan_gather(c, st, y.slots, slot_stride_for(chunk_sz), b, bn, d_dst, dst_cap);
     }
     HIPCHK(c, hipEventRecord(c->ev[0][1], st));
     HIPCHK(c, hipEventRecord(c->ev[0][2], st));
     HIPCHK(c, hipEventRecord(c->ev[0][3], st));
-    HIPCHK(c, hipMemcpyAsync(c->h_running, c->d_running, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(c->h_overflow, c->d_overflow, 4, hipMemcpyDeviceToHost, st));
+    QZD_TRY(publish_totals(c, st));
     HIPCHK(c, hipEventRecord(c->ev_end, st));
-    HIPCHK(c, hipGetLastError());
     return QZD_OK;
+}
+
+/* Every deflate call comes through here: parameter checks, then the path for its level and size.
+ * cdesc (device memory, or NULL): per-chunk length / closes-its-stream flag of a coalesced launch (qzk_chunk_len);
+ * h_src (or NULL): the input is still in host memory and is copied to d_src on the way */
+static int deflate_enqueue(qzd_ctx *c, const uint8_t *d_src, uint64_t n, uint32_t chunk_sz, int level,
+                           int last, uint8_t *d_dst, uint64_t dst_cap, const uint32_t *cdesc, const uint8_t *h_src = NULL)
+{
+    if (!c || !d_dst || (n && !d_src)) return QZD_ERR_PARAM;
+    if (chunk_sz < 1024 || chunk_sz > 512 * 1024 || (chunk_sz & (chunk_sz - 1))) return QZD_ERR_PARAM;
+    if (level < 1 || level > 9) { snprintf(c->err, sizeof(c->err), "deflate level %d: zlib has levels 1-9", level); return QZD_ERR_UNSUPPORTED; }
+    if (n > ((uint64_t)1 << 32)) return QZD_ERR_PARAM;
+    hipSetDevice(c->device);
+    const uint32_t nchunks = n ? (uint32_t)((n + chunk_sz - 1) / chunk_sz) : 1;
+    /* level 1: one chunk per wave (K1, window speculation over the four-newest table); levels 2-9: zlib's own loop
+     * and tables, one chunk per LANE (K1b).  QATZIP_AMD_DEFLATE=lane takes level 1 through K1b as well. */
+    const char *force = getenv("QATZIP_AMD_DEFLATE");
+    if ((level != 1 || (force && force[0] == 'l')) && h_src && n) { HIPCHK(c, hipMemcpyAsync((void *)d_src, h_src, n, hipMemcpyHostToDevice, c->st[0])); HIPCHK(c, hipStreamSynchronize(c->st[0])); }    /* (not the null stream: it would wait for every blocking stream of the process) */
+    /* the lazy levels have their own, parallel, path; QATZIP_AMD_LAZY=0 sends them through K1b instead */
+    const char *lz = getenv("QATZIP_AMD_LAZY");
+    if (level >= 4 && !(lz && lz[0] == '0')) return deflate_lazy_path(c, d_src, n, chunk_sz, level, last, d_dst, dst_cap, nchunks, cdesc);
+    if (level != 1 || (force && force[0] == 'l')) return deflate_lane_path(c, d_src, n, chunk_sz, level, last, d_dst, dst_cap, nchunks, cdesc);
+    /* Two parse kernels for level 1.  A call that fills the chip gives every wave a chunk of its own (K1,
+     * qzk_lz77_pull_kernel: 4096 chunks in flight hide each other's latency; throughput).  A launch of at most one chunk
+     * per CU - a lone qzCompress of a block or two, the requests a few threads have in flight - gives every chunk a
+     * whole CU instead (K1w, qzk_lz77_wide_kernel: the chunk, prev[] and the window's work on chip; latency: a chunk
+     * takes about half the time one wave needs).  QATZIP_AMD_K1=wide / pull forces one of them. */
+    const char *k1 = getenv("QATZIP_AMD_K1");
+    const bool force_wide = k1 && k1[0] == 'w', force_pull = k1 && k1[0] == 'p';
+    if (chunk_sz <= 65536 && (force_wide || (!force_pull && nchunks <= c->cus + c->cus / 2))) {      /* measured crossover: profiles/r4_k1_crossover.txt */
+        if (h_src && n) { HIPCHK(c, hipMemcpyAsync((void *)d_src, h_src, n, hipMemcpyHostToDevice, c->st[0])); HIPCHK(c, hipStreamSynchronize(c->st[0])); }
+        return deflate_wide_path(c, d_src, n, chunk_sz, last, d_dst, dst_cap, nchunks, cdesc);
+    }
+    return deflate_k1_path(c, d_src, n, chunk_sz, last, d_dst, dst_cap, nchunks, cdesc, h_src);
 }
 
 extern "C" int qzd_deflate_raw_async(qzd_ctx *c, const uint8_t *d_src, uint64_t n, uint32_t chunk_sz, int level,
@@ -991,13 +976,7 @@ extern "C" int qzd_deflate_slots(qzd_ctx *c, const uint8_t *d_src, uint32_t nslo
     if (!c || !h_cdesc || !nslots) return QZD_ERR_PARAM;
     hipSetDevice(c->device);
     for (uint32_t k = 0; k < nslots; k++) if ((h_cdesc[k] & 0x7fffffffu) > chunk_sz) return QZD_ERR_PARAM;
-    if (nslots > c->cdesc_cap) {
-        hipDeviceSynchronize();
-        if (c->d_cdesc) hipFree(c->d_cdesc);
-        c->d_cdesc = NULL; c->cdesc_cap = 0;
-        HIPCHK(c, hipMalloc(&c->d_cdesc, (size_t)nslots * 4));
-        c->cdesc_cap = nslots;
-    }
+    QZD_TRY(grow_dev(c, (void **)&c->d_cdesc, &c->cdesc_cap, (size_t)nslots * 4));
     HIPCHK(c, hipMemcpy(c->d_cdesc, h_cdesc, (size_t)nslots * 4, hipMemcpyHostToDevice));
     int rc = deflate_enqueue(c, d_src, (uint64_t)nslots * chunk_sz, chunk_sz, level, 0, d_dst, dst_cap, c->d_cdesc);
     if (rc) return rc;
@@ -1108,28 +1087,13 @@ static int lz4_compress_frames_impl(qzd_ctx *c, const uint8_t *d_src, uint64_t n
     hipSetDevice(c->device);
     const uint32_t nfr = n ? (uint32_t)((n + frame_sz - 1) / frame_sz) : 1;
     const uint32_t stride = (frame_sz + 15 + 4 * ((frame_sz + 65535) >> 16) + 8 + 64 + 15) & ~15u;
-    if (nfr > c->call_cap) {
-        hipDeviceSynchronize();
-        hipFree(c->d_len); hipFree(c->d_crc); hipFree(c->d_offs);
-        c->d_len = NULL; c->d_crc = NULL; c->d_offs = NULL; c->call_cap = 0;
-        HIPCHK(c, hipMalloc(&c->d_len, (size_t)nfr * 4));
-        HIPCHK(c, hipMalloc(&c->d_crc, (size_t)nfr * 4));
-        HIPCHK(c, hipMalloc(&c->d_offs, (size_t)nfr * 8));
-        c->call_cap = nfr;
-    }
+    QZD_TRY(reserve_call_arrays(c, nfr));
     uint32_t batch = nfr < 16384u ? nfr : 16384u;
     if (linked && (uint64_t)batch * stride > (1ull << 30)) batch = std::max<uint32_t>(1u, (uint32_t)((1ull << 30) / stride));   /* slots of a gigabyte at most */
-    if ((size_t)batch * stride > c->slot_cap) {
-        hipDeviceSynchronize();
-        for (int i = 0; i < QZD_NBUF; i++) { hipFree(c->slots[i]); c->slots[i] = NULL; }
-        c->slot_cap = 0;
-        for (int i = 0; i < QZD_NBUF; i++) HIPCHK(c, hipMalloc(&c->slots[i], (size_t)batch * stride));
-        c->slot_cap = (size_t)batch * stride;
-    }
+    QZD_TRY(grow_dev(c, (void **)&c->lz4_slots, &c->slot_cap, (size_t)batch * stride));
+    uint8_t *const slots = c->lz4_slots;
     hipStream_t st = c->st[0];
-    HIPCHK(c, hipMemsetAsync(c->d_running, 0, 8, st));
-    HIPCHK(c, hipMemsetAsync(c->d_overflow, 0, 4, st));
-    HIPCHK(c, hipEventRecord(c->ev_begin, st));
+    QZD_TRY(call_begin(c, st, nfr, c->nbatches));      /* (the stage events of qzd_last_timing stay the last deflate call's) */
     for (uint32_t b = 0; b < nfr; b += batch) {
         const uint32_t bn = nfr - b < batch ? nfr - b : batch;
         const uint64_t boff = (uint64_t)b * frame_sz;
@@ -1143,46 +1107,37 @@ static int lz4_compress_frames_impl(qzd_ctx *c, const uint8_t *d_src, uint64_t n
             /* one wave per chunk; the call's last chunk is a one-block frame when it is 64 KB or less */
             const bool tail_small = b + bn == nfr && n - (uint64_t)(nfr - 1) * frame_sz <= QZK_LZ4_MAXBLK;
             const uint32_t nl = tail_small ? bn - 1 : bn;
-            if (nl) hipLaunchKernelGGL(qzk_lz4c_linked_many_kernel, dim3(nl), dim3(64), 0, st, d_src + boff, n - boff, frame_sz, nl, c->slots[0], stride, c->d_len + b);
+            if (nl) hipLaunchKernelGGL(qzk_lz4c_linked_many_kernel, dim3(nl), dim3(64), 0, st, d_src + boff, n - boff, frame_sz, nl, slots, stride, c->d_len + b);
             if (tail_small) {
                 const uint64_t toff = (uint64_t)(nfr - 1) * frame_sz;
-                hipLaunchKernelGGL(qzk_lz4c_kernel, dim3(1), dim3(64), 0, st, d_src + toff, n - toff, (uint32_t)QZK_LZ4_MAXBLK, 1u, c->slots[0] + (size_t)(bn - 1) * stride, stride, c->d_len + nfr - 1, hw_hdr);
+                hipLaunchKernelGGL(qzk_lz4c_kernel, dim3(1), dim3(64), 0, st, d_src + toff, n - toff, (uint32_t)QZK_LZ4_MAXBLK, 1u, slots + (size_t)(bn - 1) * stride, stride, c->d_len + nfr - 1, hw_hdr);
             }
         } else if (wpc && bn > 8 * cus) {
             const uint32_t waves = std::min<uint32_t>(bn, wpc * cus);
             if (waves > c->lz4tab_waves) {
-                hipDeviceSynchronize();
-                if (c->d_lz4tab) hipFree(c->d_lz4tab);
-                c->d_lz4tab = NULL; c->lz4tab_waves = 0;
+                size_t had = 0;             /* (the table's capacity is kept in waves) */
+                c->lz4tab_waves = 0;
                 /* frame counter (256 B), the waves' epochs, their tables (8192 entries of 8 bytes each: 64 KiB a wave, 512 MiB for
                  * a full device) - cleared ONCE here: the epochs take the place of a clearing per frame */
                 const size_t epb = ((size_t)waves * 4 + 255) & ~(size_t)255, tb = (size_t)waves * QZK_L4C_TABW * 8;
-                HIPCHK(c, hipMalloc(&c->d_lz4tab, 256 + epb + tb));
+                QZD_TRY(grow_dev(c, (void **)&c->d_lz4tab, &had, 256 + epb + tb));
                 HIPCHK(c, hipMemsetAsync(c->d_lz4tab, 0, 256 + epb + tb, st));
                 c->lz4tab_waves = waves;
             }
             HIPCHK(c, hipMemsetAsync(c->d_lz4tab, 0, 4, st));
             {
                 const size_t epb = ((size_t)c->lz4tab_waves * 4 + 255) & ~(size_t)255;
-                hipLaunchKernelGGL(qzk_lz4c_pull_kernel, dim3(waves), dim3(64), 0, st, d_src + boff, n - boff, frame_sz, bn, c->slots[0], stride,
+                hipLaunchKernelGGL(qzk_lz4c_pull_kernel, dim3(waves), dim3(64), 0, st, d_src + boff, n - boff, frame_sz, bn, slots, stride,
                                    c->d_len + b, hw_hdr, (uint64_t *)(c->d_lz4tab + 256 + epb), (uint32_t *)(c->d_lz4tab + 256), (uint32_t *)c->d_lz4tab);
             }
         } else
-            hipLaunchKernelGGL(qzk_lz4c_kernel, dim3(bn), dim3(64), 0, st, d_src + boff, n - boff, frame_sz, bn, c->slots[0], stride, c->d_len + b, hw_hdr);
-        hipLaunchKernelGGL(qzk_scan_kernel, dim3(1), dim3(1024), 0, st, c->d_len + b, bn, c->d_offs + b, c->d_running);
-        hipLaunchKernelGGL(qzk_gather_kernel, dim3(bn), dim3(256), 0, st, c->slots[0], stride, c->d_len + b, c->d_offs + b, bn, d_dst, dst_cap, c->d_overflow);
+            hipLaunchKernelGGL(qzk_lz4c_kernel, dim3(bn), dim3(64), 0, st, d_src + boff, n - boff, frame_sz, bn, slots, stride, c->d_len + b, hw_hdr);
+        launch_scan_gather(c, st, slots, stride, b, bn, d_dst, dst_cap);
     }
     HIPCHK(c, hipEventRecord(c->ev_end, st));
-    HIPCHK(c, hipMemcpyAsync(c->h_running, c->d_running, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(c->h_overflow, c->d_overflow, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    HIPCHK(c, hipGetLastError());
-    c->last_nchunks = nfr;
-    if (*c->h_overflow) { snprintf(c->err, sizeof(c->err), "destination too small"); return QZD_ERR_DSTCAP; }
-    *h_out_len = *c->h_running;
+    QZD_TRY(publish_totals(c, st));
+    QZD_TRY(finish_sync_call(c, st, h_out_len));
     if (h_frame_len) HIPCHK(c, hipMemcpy(h_frame_len, c->d_len, (size_t)nfr * 4, hipMemcpyDeviceToHost));
-    float t = 0;
-    if (hipEventElapsedTime(&t, c->ev_begin, c->ev_end) == hipSuccess) c->ms[3] = t;
     return QZD_OK;
 }
 
@@ -1203,8 +1158,6 @@ extern "C" int qzd_lz4_compress_linked(qzd_ctx *c, const uint8_t *d_src, uint64_
     HIPCHK(c, hipStreamSynchronize(st));
     HIPCHK(c, hipGetLastError());
     *h_out_len = *c->h_overflow;
-    float t = 0;
-    if (hipEventElapsedTime(&t, c->ev_begin, c->ev_end) == hipSuccess) c->ms[3] = t;
     return QZD_OK;
 }
 
@@ -1233,31 +1186,14 @@ static int lz4hc_impl(qzd_ctx *c, const uint8_t *d_src, uint64_t n, uint32_t fra
     const uint32_t stride = (QZK_LZ4_MAXBLK + QZK_HC_HDRMAX + 4 + 8 + 15) & ~15u;
     const uint32_t B = nb < QZD_HC_BATCH ? nb : QZD_HC_BATCH;
     const size_t headb = (size_t)B * QZK_HC_HSIZE * 4, chainb = (size_t)B * QZK_HC_WIN * 2, slotb = (size_t)B * stride;
-    const size_t need = headb + chainb + slotb;
-    if (need > c->lane_cap) {
-        hipDeviceSynchronize();
-        if (c->d_lane) hipFree(c->d_lane);
-        c->d_lane = NULL; c->lane_cap = 0;
-        HIPCHK(c, hipMalloc(&c->d_lane, need));
-        c->lane_cap = need;
-    }
-    if (nb > c->call_cap) {
-        hipDeviceSynchronize();
-        hipFree(c->d_len); hipFree(c->d_crc); hipFree(c->d_offs);
-        c->d_len = NULL; c->d_crc = NULL; c->d_offs = NULL; c->call_cap = 0;
-        HIPCHK(c, hipMalloc(&c->d_len, (size_t)nb * 4));
-        HIPCHK(c, hipMalloc(&c->d_crc, (size_t)nb * 4));
-        HIPCHK(c, hipMalloc(&c->d_offs, QZD_OFFS_BYTES(nb)));
-        c->call_cap = nb;
-    }
+    QZD_TRY(grow_dev(c, (void **)&c->d_lane, &c->lane_cap, headb + chainb + slotb));
+    QZD_TRY(reserve_call_arrays(c, nb));
     uint32_t *head = (uint32_t *)c->d_lane;
     uint16_t *chain = (uint16_t *)(c->d_lane + headb);
     uint8_t *slots = c->d_lane + headb + chainb;
     uint32_t *xx = c->d_crc;                                        /* one content hash per frame (nfr <= nb) */
     hipStream_t st = c->st[0];
-    HIPCHK(c, hipMemsetAsync(c->d_running, 0, 8, st));
-    HIPCHK(c, hipMemsetAsync(c->d_overflow, 0, 4, st));
-    HIPCHK(c, hipEventRecord(c->ev_begin, st));
+    QZD_TRY(call_begin(c, st, nb, c->nbatches));
     /* the content checksums on a stream of their own: a frame's XXH32 is one wave's serial work (a gigabyte takes most of a
      * second), the rounds below go on beside it and only the finish kernel waits for it */
     HIPCHK(c, hipStreamWaitEvent(c->st[1], c->ev_begin, 0));
@@ -1269,21 +1205,15 @@ static int lz4hc_impl(qzd_ctx *c, const uint8_t *d_src, uint64_t n, uint32_t fra
         hipLaunchKernelGGL(qzk_lz4hc_chain_kernel, dim3(bn), dim3(64), 0, st, d_src, n, frame_sz, bpf, g0, bn, head, chain);
         hipLaunchKernelGGL(qzk_lz4hc_parse_kernel, dim3(bn), dim3(64), 0, st, d_src, n, frame_sz, bpf, g0, bn,
                            (const uint16_t *)chain, slots, stride, c->d_len + g0, hw_hdr, attempts);
-        hipLaunchKernelGGL(qzk_scan_kernel, dim3(1), dim3(1024), 0, st, c->d_len + g0, bn, c->d_offs + g0, c->d_running);
-        hipLaunchKernelGGL(qzk_gather_kernel, dim3(bn), dim3(256), 0, st, slots, stride, c->d_len + g0, c->d_offs + g0, bn, d_dst, dst_cap, c->d_overflow);
+        launch_scan_gather(c, st, slots, stride, g0, bn, d_dst, dst_cap);
     }
     /* end marks and checksums of all frames at once, behind the last round and behind the hashes */
     HIPCHK(c, hipStreamWaitEvent(st, c->done[1], 0));
     hipLaunchKernelGGL(qzk_lz4hc_finish_kernel, dim3((nfr + 63) / 64), dim3(64), 0, st, n, frame_sz, bpf, 0u, nb, nb,
                        (const uint64_t *)c->d_offs, (const uint32_t *)c->d_len, (const uint32_t *)xx, d_dst, dst_cap);
     HIPCHK(c, hipEventRecord(c->ev_end, st));
-    HIPCHK(c, hipMemcpyAsync(c->h_running, c->d_running, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(c->h_overflow, c->d_overflow, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    HIPCHK(c, hipGetLastError());
-    c->last_nchunks = nb;
-    if (*c->h_overflow) { snprintf(c->err, sizeof(c->err), "destination too small"); return QZD_ERR_DSTCAP; }
-    *h_out_len = *c->h_running;
+    QZD_TRY(publish_totals(c, st));
+    QZD_TRY(finish_sync_call(c, st, h_out_len));
     if (h_frame_len) {
         std::vector<uint32_t> bl(nb);
         HIPCHK(c, hipMemcpy(bl.data(), c->d_len, (size_t)nb * 4, hipMemcpyDeviceToHost));
@@ -1293,8 +1223,6 @@ static int lz4hc_impl(qzd_ctx *c, const uint8_t *d_src, uint64_t n, uint32_t fra
             h_frame_len[f] = sum;
         }
     }
-    float t = 0;
-    if (hipEventElapsedTime(&t, c->ev_begin, c->ev_end) == hipSuccess) c->ms[3] = t;
     return QZD_OK;
 }
 extern "C" int qzd_lz4hc_compress_frames(qzd_ctx *c, const uint8_t *d_src, uint64_t n, uint32_t frame_sz, int level,
@@ -1341,8 +1269,6 @@ extern "C" int qzd_lz4_decompress_frames(qzd_ctx *c, const uint8_t *d_comp, uint
     HIPCHK(c, hipMemcpyAsync(h_res, d_res, rb, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     HIPCHK(c, hipGetLastError());
-    float t = 0;
-    if (hipEventElapsedTime(&t, c->ev_begin, c->ev_end) == hipSuccess) c->ms[3] = t;
     return QZD_OK;
 }
 

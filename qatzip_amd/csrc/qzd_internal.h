@@ -26,8 +26,8 @@ struct qzd_ctx {
     bool helper;                                            /* a piece's helper context (qzd_inflate_stream_from_host): one stream */
     hipEvent_t done[QZD_NBUF], k1done[QZD_NBUF];
     uint32_t cus;                                   /* compute units of the device */
-    /* output slots of the LZ4 frame kernel (the deflate pipeline's scratch lives in the device's pool, qzd_k1pool) */
-    uint8_t *slots[QZD_NBUF];
+    /* output slots of the LZ4 frame kernels (the deflate pipeline's scratch lives in the device's pool, qzd_k1pool) */
+    uint8_t *lz4_slots;
     /* K1 (persistent pull kernel): one candidate table (65536 x QZK_K1_WAVES entries of 16 bytes = 4 MiB) per resident
      * workgroup, one chunk counter per buffer set */
     /* The tables belong to the DEVICE, not to the context (qzd_k1pool): every session of a process on one GPU parses
@@ -41,8 +41,8 @@ struct qzd_ctx {
     /* decode counters since the last reset (qzd_inflate_stats): segments the K-lane phase A handed back to the serial one,
      * and two_phase() calls that handed back more than the hand-back area holds and were re-run with one lane a segment */
     uint64_t inf_handback_acc, inf_k1rerun_acc;
-    size_t slot_cap;
-    /* per-call arrays */
+    size_t slot_cap;                                /* bytes of lz4_slots */
+    /* per-call arrays (reserve_call_arrays) */
     uint32_t *d_len, *d_crc; uint64_t *d_offs; uint32_t call_cap;
     uint64_t *d_running; uint32_t *d_overflow;
     uint64_t *h_running; uint32_t *h_overflow;      /* pinned */
@@ -50,7 +50,7 @@ struct qzd_ctx {
     uint32_t *h_wm;                                 /* pinned, read by qzk_lz77_pull_kernel: [0] chunks of host input landed, [1] a wave gave up waiting */
     /* timing */
     hipEvent_t ev[QZD_NBUF][4]; hipEvent_t ev_begin, ev_end;
-    uint32_t nbatches; float ms[4];
+    uint32_t nbatches;
     uint32_t last_nchunks;
     /* generic small scratch for the decompress side: device + pinned host mirror */
     uint8_t *d_aux, *h_aux; size_t aux_cap;
@@ -58,8 +58,8 @@ struct qzd_ctx {
      * and sends each range to so_host behind its launch; so_nat[i] = array index of the segment that is i-th in the output */
     uint8_t *so_host; const uint32_t *so_nat; uint64_t so_sent; hipEvent_t so_ev[8];
     uint8_t *d_big; size_t big_cap; uint32_t big_small;   /* device-only scratch (per-segment decode tables of K3b); calls in a row that needed under a quarter of it */
-    uint32_t *d_cdesc; uint32_t cdesc_cap;          /* per-slot descriptors of a coalesced launch (qzd_deflate_slots) */
-    uint8_t *d_lane; size_t lane_cap;               /* device-only scratch of the one-chunk-per-lane compress path (K1b) */
+    uint32_t *d_cdesc; size_t cdesc_cap;            /* per-slot descriptors of a coalesced launch (qzd_deflate_slots); capacity in bytes */
+    uint8_t *d_lane; size_t lane_cap;               /* device-only scratch of the lane, wide, lazy and LZ4-HC compress paths (carve_symbols) */
     float inf_ms[4];
     bool no_stream_in;              /* this call is the batched retry of a launch that gave up waiting for its input */
     /* device arrays of the last two-phase inflate (phase A done, phase B still to run): two_phase() / two_phase_resolve() */

@@ -204,3 +204,56 @@ def test_lz4_session_in_hardware_path_framing():
         rc, used, out, _ = s.compress(src, 1, cap=first_two + 5)
         assert rc == A.QZ_BUF_ERROR and used == 2 * hw and out == full[:first_two]
         s.close()
+
+
+def test_one_context_lz4_then_deflate_moved_by_the_launch():
+    """The compress paths of a context share its per-call arrays (lengths, CRCs, offsets), whichever path allocated them:
+    2048 LZ4 frames of 64 KB in a fresh context, then the same 128 MiB as 2048 deflate chunks through the one launch
+    that moves the stream itself (QATZIP_AMD_K1_OUT=launch: front word and published lengths behind the offsets), then
+    the LZ4 call again.  Every result is what the path gives on its own."""
+    import os
+    import zlib
+    import numpy as np
+    import qatzip_amd
+    base = datagen.gen("silesia", 16 << 20, 9)
+    text = datagen.gen("text", 16 << 20, 10)
+    src = np.concatenate([base, base[::-1], np.roll(base, 12345), base ^ 1, text, text[::-1], np.roll(base, -999), text ^ 1])
+    n, fs = src.size, 65536
+    assert n == 128 << 20
+    nfr = n // fs
+    c = qatzip_amd.Context(0)
+    bufs = []
+    try:
+        d_src = c.alloc(n); bufs.append(d_src); d_src.upload(src)
+        d_l1 = c.alloc(n + nfr * 64 + 4096); d_l2 = c.alloc(n + nfr * 64 + 4096)
+        d_z = c.alloc(qatzip_amd.max_deflate_len(n, fs))
+        d_out = c.alloc(n)
+        bufs += [d_l1, d_l2, d_z, d_out]
+        t1, l1 = c.lz4_compress_frames(d_src, n, d_l1, fs)
+        old = os.environ.get("QATZIP_AMD_K1_OUT"), os.environ.get("QATZIP_AMD_K1")
+        os.environ["QATZIP_AMD_K1_OUT"] = "launch"; os.environ["QATZIP_AMD_K1"] = "pull"
+        try:
+            zn, _ = c.deflate_raw(d_src, n, fs, 1, 1, d_z)
+        finally:
+            for k, v in zip(("QATZIP_AMD_K1_OUT", "QATZIP_AMD_K1"), old):
+                if v is None:
+                    os.environ.pop(k, None)
+                else:
+                    os.environ[k] = v
+        t2, l2 = c.lz4_compress_frames(d_src, n, d_l2, fs)
+        got = d_z.download(zn).tobytes()
+        assert zlib.decompress(got, -15) == src.tobytes()
+        exp = O.sw_compress("RAW", src[:4 << 20].tobytes(), 65536, 1, last=0)[2]
+        assert got[:len(exp)] == exp
+        assert t1 == t2 and (l1 == l2).all()
+        assert np.array_equal(d_l1.download(t1), d_l2.download(t2))
+        segs, io = [], 0
+        for i in range(nfr):
+            segs.append((io, i * fs, int(l1[i]), fs)); io += int(l1[i])
+        res = c.lz4_decompress_frames(d_l1, d_out, segs)
+        assert (res["status"] == 0).all() and (res["out_len"] == fs).all()
+        assert np.array_equal(d_out.download(n), src)
+    finally:
+        for b in bufs:
+            b.free()
+        c.close()
