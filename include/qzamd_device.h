@@ -207,10 +207,24 @@ int qzd_lz4hc_compress_frames_hw(qzd_ctx *ctx, const uint8_t *d_src, uint64_t n,
                                  uint64_t dst_cap, uint64_t *h_out_len, uint32_t *h_frame_len);
 int qzd_lz4hc_compress_linked(qzd_ctx *ctx, const uint8_t *d_src, uint64_t n, int level, uint8_t *d_dst, uint64_t dst_cap,
                               uint64_t *h_out_len);
-/* decode nsegs frames (any block mode, content checksum verified on the GPU); replaces LZ4F_decompress,
- * src/qatzip_sw.c:496 */
+/* decode nsegs frames (any block mode; block checksums and the content checksum verified on the GPU); replaces
+ * LZ4F_decompress, src/qatzip_sw.c:496, and answers as it does: a wrong block checksum is a data error whether or not the
+ * frame has a content checksum, and in a frame of independent blocks (FLG bit 5) a match that reaches in front of its own
+ * block is one too.
+ * Routes.  A frame of up to 65571 bytes (the largest with one 64 KB block) is one wave's work, and a call of such frames is
+ * one launch.  A larger frame is a candidate: if its blocks are independent, it has at least two of them and no more than
+ * in_len / 1024 + 64, every block is decoded by a wave of its own (plan, size, scan, block and finish kernels, one small
+ * device-to-host read between the first and the rest; the table and scratch come out of the context's aux area, about
+ * 24 bytes per KiB of candidate input).  Linked frames and all other candidates stay on one wave, in one launch with the
+ * small frames.  Both routes give the same bytes and the same {0, in_used, out_len} for every frame liblz4 accepts and a
+ * non-zero status for every frame it refuses - the same code where the cause is the same; a frame whose output exceeds
+ * out_cap is -2 on the block route before a byte of it is written.  in_used / out_len of a FAILED frame are unspecified on
+ * the block route.  No route ever stores beyond a segment's out_cap. */
 int qzd_lz4_decompress_frames(qzd_ctx *ctx, const uint8_t *d_comp, uint8_t *d_out, const void *h_segs,
                               uint32_t nsegs, void *h_res);
+/* developer switch for the above: 0 auto, 1 every frame on one wave, 2 a wave per block for every candidate that qualifies
+ * (today auto and 2 qualify the same frames).  A context starts with QATZIP_AMD_LZ4D=auto|wave|blocks. */
+int qzd_lz4_decode_route(qzd_ctx *ctx, int route);
 
 /* ------------------------------------------------------------------ one member from several GPUs
  *

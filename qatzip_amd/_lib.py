@@ -59,6 +59,8 @@ def load(build_if_missing=True):
     L.qzd_lz4_compress_frames_hw.argtypes = L.qzd_lz4_compress_frames.argtypes
     L.qzd_lz4_compress_linked.argtypes = [vp, u8p, C.c_uint64, u8p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.qzd_lz4_decompress_frames.argtypes = [vp, u8p, u8p, vp, C.c_uint32, vp]
+    if hasattr(L, "qzd_lz4_decode_route"):                  # (variant libraries built from older sources lack it)
+        L.qzd_lz4_decode_route.argtypes = [vp, C.c_int]
     L.qzd_lz4hc_compress_frames.argtypes = [vp, u8p, C.c_uint64, C.c_uint32, C.c_int, u8p, C.c_uint64, C.POINTER(C.c_uint64), vp]
     L.qzd_lz4hc_compress_frames_hw.argtypes = L.qzd_lz4hc_compress_frames.argtypes
     L.qzd_lz4hc_compress_linked.argtypes = [vp, u8p, C.c_uint64, C.c_int, u8p, C.c_uint64, C.POINTER(C.c_uint64)]
@@ -97,7 +99,7 @@ def exported_symbols():
             "qzd_h2d", "qzd_d2h", "qzd_host_alloc_pinned", "qzd_host_free_pinned", "qzd_deflate_raw",
             "qzd_deflate_raw_async", "qzd_sync", "qzd_result", "qzd_last_timing", "qzd_inflate_segments",
             "qzd_inflate_stream", "qzd_crc32", "qzd_crc32_ranges", "qzd_last_inflate_timing", "qzd_inflate_scratch_bytes",
-            "qzd_lz4_compress_frames", "qzd_lz4_compress_frames_hw", "qzd_lz4_decompress_frames", "qzd_chunk_lens", "qzd_batch_chunks", "qzd_k1_stats", "qzd_inflate_stats",
+            "qzd_lz4_compress_frames", "qzd_lz4_compress_frames_hw", "qzd_lz4_decompress_frames", "qzd_lz4_decode_route", "qzd_chunk_lens", "qzd_batch_chunks", "qzd_k1_stats", "qzd_inflate_stats",
             "qzd_adler32_chunks", "qzd_adler32_combine", "qzd_stream_copy_peak", "qzd_deflate_raw_from_host",
             "qzd_deflate_slots", "qzd_inflate_stream_to_host", "qzd_inflate_stream_from_host", "qzamd_async_stats", "qzd_shard_root_create",
             "qzd_shard_attach", "qzd_shard_slot_handle", "qzd_shard_attach_slot", "qzd_lz4_compress_linked", "qzd_shard_put", "qzd_shard_finish", "qzd_shard_close", "qzd_crc32_combine",
@@ -258,8 +260,18 @@ class Context:
             self._chk(self.L.qzd_lz4_compress_linked(self.h, d_src.ptr, n, d_dst.ptr, d_dst.nbytes, C.byref(ol)))
         return ol.value
 
-    def lz4_decompress_frames(self, d_comp, d_out, segs):
-        """segs: list of (in_off, out_off, in_len, out_cap) -> structured results (status, in_used, out_len)"""
+    LZ4D_ROUTES = {"auto": 0, "wave": 1, "blocks": 2}
+
+    def lz4_decode_route(self, route):
+        """how lz4_decompress_frames treats frames above 65571 bytes from now on: "auto", "wave" (every frame on one wave)
+        or "blocks" (a wave per block for every frame of independent blocks that qualifies)"""
+        self._chk(self.L.qzd_lz4_decode_route(self.h, self.LZ4D_ROUTES[route]))
+
+    def lz4_decompress_frames(self, d_comp, d_out, segs, route=None):
+        """segs: list of (in_off, out_off, in_len, out_cap) -> structured results (status, in_used, out_len).  route: see
+        lz4_decode_route; given here it holds for this call and for those after it"""
+        if route is not None:
+            self.lz4_decode_route(route)
         sa = np.array([tuple(s) for s in segs], dtype=LZ4SEG_DT)
         res = np.zeros(len(segs), LZ4RES_DT)
         self._chk(self.L.qzd_lz4_decompress_frames(self.h, d_comp.ptr, d_out.ptr, sa.ctypes.data, len(segs), res.ctypes.data))

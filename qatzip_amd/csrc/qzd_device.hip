@@ -253,6 +253,8 @@ static int ctx_create(int device, qzd_ctx **out, bool helper)
         if (hipMalloc(&c->k1_counter, QZD_NBUF * 4) != hipSuccess) QZD_CREATE_FAIL;
     }
     if (hipMalloc(&c->d_running, 8) != hipSuccess || hipMalloc(&c->d_overflow, 4) != hipSuccess) QZD_CREATE_FAIL;
+    /* QATZIP_AMD_LZ4D=auto|wave|blocks: how qzd_lz4_decompress_frames routes large frames (qzd_lz4_decode_route) */
+    if (const char *e = getenv("QATZIP_AMD_LZ4D")) c->lz4d_route = !strcmp(e, "wave") ? 1 : !strcmp(e, "blocks") ? 2 : 0;
     hipHostMalloc((void **)&c->h_running, 8, hipHostMallocDefault);
     hipHostMalloc((void **)&c->h_overflow, 4, hipHostMallocDefault);
     /* watermark of a launch whose input is still arriving: read by the kernel over the link, so coherent + mapped */
@@ -1247,14 +1249,103 @@ extern "C" int qzd_lz4hc_compress_linked(qzd_ctx *c, const uint8_t *d_src, uint6
     return lz4hc_impl(c, d_src, n, (uint32_t)n, level, 0, d_dst, dst_cap, h_out_len, NULL);
 }
 
+/* 0 auto, 1 every frame on one wave (qzk_lz4d_kernel), 2 a wave per block for every candidate frame that qualifies */
+extern "C" int qzd_lz4_decode_route(qzd_ctx *c, int route)
+{
+    if (!c || route < 0 || route > 2) return QZD_ERR_PARAM;
+    c->lz4d_route = route;
+    return QZD_OK;
+}
+
+/* blocks a frame of independent blocks must have to go a wave per block when the route is auto */
+#define QZD_LZ4D_AUTO_MINBLK 2u
+
+/* a call with candidate frames (above QZK_LZ4_CAND bytes): the plan kernel, one read of its verdicts, then the frames it left
+ * to qzk_lz4d_kernel together with the small ones in one launch, and the block kernels for the rest (qzk_lz4.h, K5b).
+ * Everything lives in the aux pair; `shares` = the table entries of all candidates */
+static int lz4d_with_blocks(qzd_ctx *c, const uint8_t *d_comp, uint8_t *d_out, const qzk_lz4seg *hs, uint32_t nsegs, void *h_res,
+                            uint32_t ncand, uint32_t shares)
+{
+    const size_t sb = (size_t)nsegs * sizeof(qzk_lz4seg), rb = (size_t)nsegs * sizeof(qzk_lz4res);
+    size_t off = 0;
+    auto take = [&off](size_t n) { const size_t o = off; off = (off + n + 15) & ~(size_t)15; return o; };
+    const size_t o_segs = take(sb), o_res = take(rb), o_cand = take((size_t)ncand * sizeof(qzk_lz4cand)),
+                 o_plan = take((size_t)ncand * sizeof(qzk_lz4plan)), o_fr = take((size_t)ncand * sizeof(qzk_lz4fr)),
+                 o_segs2 = take(sb), o_res2 = take(rb), o_idx2 = take((size_t)nsegs * 4),
+                 o_tab = take((size_t)shares * sizeof(qzk_lz4blk)), o_dlen = take((size_t)shares * 4), o_ooff = take((size_t)shares * 4);
+    int rc = qzd_aux_reserve(c, off + 64);
+    if (rc) return rc;
+    uint8_t *d = c->d_aux, *h = c->h_aux;
+    qzk_lz4seg *d_segs = (qzk_lz4seg *)(d + o_segs), *d_segs2 = (qzk_lz4seg *)(d + o_segs2), *h_segs2 = (qzk_lz4seg *)(h + o_segs2);
+    qzk_lz4res *d_res = (qzk_lz4res *)(d + o_res), *d_res2 = (qzk_lz4res *)(d + o_res2), *h_res2 = (qzk_lz4res *)(h + o_res2);
+    qzk_lz4cand *d_cand = (qzk_lz4cand *)(d + o_cand), *h_cand = (qzk_lz4cand *)(h + o_cand);
+    qzk_lz4plan *d_plan = (qzk_lz4plan *)(d + o_plan), *h_plan = (qzk_lz4plan *)(h + o_plan);
+    qzk_lz4fr *d_fr = (qzk_lz4fr *)(d + o_fr), *h_fr = (qzk_lz4fr *)(h + o_fr);
+    uint32_t *h_idx2 = (uint32_t *)(h + o_idx2);
+    qzk_lz4blk *d_tab = (qzk_lz4blk *)(d + o_tab);
+    uint32_t *d_dlen = (uint32_t *)(d + o_dlen), *d_ooff = (uint32_t *)(d + o_ooff);
+    uint32_t k = 0, first = 0;
+    for (uint32_t i = 0; i < nsegs; i++) if (hs[i].in_len > QZK_LZ4_CAND) {
+        qzk_lz4cand cd; cd.seg = i; cd.first = first; cd.cap = QZK_LZ4_SHARE(hs[i].in_len); cd.pad = 0;
+        h_cand[k++] = cd; first += cd.cap;
+    }
+    hipStream_t st = c->st[0];
+    HIPCHK(c, hipMemcpyAsync(d_segs, hs, sb, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(d_cand, h_cand, (size_t)ncand * sizeof(qzk_lz4cand), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipEventRecord(c->ev_begin, st));
+    hipLaunchKernelGGL(qzk_lz4d_plan_kernel, dim3(ncand), dim3(64), 0, st, d_comp, d_segs, d_cand, ncand,
+                       c->lz4d_route == 2 ? 2u : QZD_LZ4D_AUTO_MINBLK, d_tab, d_plan, d_res);
+    HIPCHK(c, hipMemcpyAsync(h_plan, d_plan, (size_t)ncand * sizeof(qzk_lz4plan), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    uint32_t nfr = 0, nw = 0, n2 = 0;
+    k = 0;
+    for (uint32_t i = 0; i < nsegs; i++) {
+        if (hs[i].in_len > QZK_LZ4_CAND) {
+            const qzk_lz4plan pl = h_plan[k]; const qzk_lz4cand cd = h_cand[k]; k++;
+            if (pl.route == QZK_LZ4P_DONE) continue;
+            if (pl.route == QZK_LZ4P_BLOCKS) {
+                qzk_lz4fr F; F.seg = i; F.first = cd.first; F.nblk = pl.nblk; F.wbase = nw; F.end = pl.end; F.flags = pl.flags; F.status = 0; F.total = 0;
+                h_fr[nfr++] = F; nw += pl.nblk;
+                continue;
+            }
+        }
+        h_segs2[n2] = hs[i]; h_idx2[n2] = i; n2++;
+    }
+    if (nfr) HIPCHK(c, hipMemcpyAsync(d_fr, h_fr, (size_t)nfr * sizeof(qzk_lz4fr), hipMemcpyHostToDevice, st));
+    if (n2) {
+        HIPCHK(c, hipMemcpyAsync(d_segs2, h_segs2, (size_t)n2 * sizeof(qzk_lz4seg), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(qzk_lz4d_kernel, dim3(n2), dim3(64), 0, st, d_comp, d_out, d_segs2, d_res2, n2);
+    }
+    if (nfr) {
+        hipLaunchKernelGGL(qzk_lz4d_size_kernel, dim3(nw), dim3(64), 0, st, d_comp, d_segs, d_tab, d_fr, nfr, nw, d_dlen);
+        hipLaunchKernelGGL(qzk_lz4d_scan_kernel, dim3(nfr), dim3(64), 0, st, d_segs, d_fr, nfr, d_dlen, d_ooff);
+        hipLaunchKernelGGL(qzk_lz4d_block_kernel, dim3(nw), dim3(64), 0, st, d_comp, d_out, d_segs, d_tab, d_fr, nfr, nw, d_dlen, d_ooff);
+        hipLaunchKernelGGL(qzk_lz4d_finish_kernel, dim3(nfr), dim3(64), 0, st, d_comp, d_out, d_segs, d_fr, nfr, d_res);
+    }
+    HIPCHK(c, hipEventRecord(c->ev_end, st));
+    HIPCHK(c, hipMemcpyAsync(h_res, d_res, rb, hipMemcpyDeviceToHost, st));
+    if (n2) HIPCHK(c, hipMemcpyAsync(h_res2, d_res2, (size_t)n2 * sizeof(qzk_lz4res), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, hipGetLastError());
+    for (uint32_t j = 0; j < n2; j++) ((qzk_lz4res *)h_res)[h_idx2[j]] = h_res2[j];
+    return QZD_OK;
+}
+
 /* decode nsegs LZ4 frames {u64 in_off, u64 out_off, u32 in_len, u32 out_cap} -> {i32 status, u32 in_used, u32 out_len, u32 pad};
- * content checksums are verified on the GPU (XXH32) */
+ * block and content checksums are verified on the GPU (XXH32).  A call without a frame above QZK_LZ4_CAND bytes is the one
+ * launch of qzk_lz4d_kernel it always was */
 extern "C" int qzd_lz4_decompress_frames(qzd_ctx *c, const uint8_t *d_comp, uint8_t *d_out, const void *h_segs,
                                          uint32_t nsegs, void *h_res)
 {
     if (!c || !h_segs || !h_res) return QZD_ERR_PARAM;
     if (nsegs == 0) return QZD_OK;
     hipSetDevice(c->device);
+    if (c->lz4d_route != 1) {
+        const qzk_lz4seg *hs = (const qzk_lz4seg *)h_segs;
+        uint32_t ncand = 0; uint64_t shares = 0;
+        for (uint32_t i = 0; i < nsegs; i++) if (hs[i].in_len > QZK_LZ4_CAND) { ncand++; shares += QZK_LZ4_SHARE(hs[i].in_len); }
+        if (ncand && shares <= 0x7fffffffull) return lz4d_with_blocks(c, d_comp, d_out, hs, nsegs, h_res, ncand, (uint32_t)shares);
+    }
     const size_t sb = (size_t)nsegs * sizeof(qzk_lz4seg), rb = (size_t)nsegs * sizeof(qzk_lz4res);
     int rc = qzd_aux_reserve(c, sb + rb + 64);
     if (rc) return rc;

@@ -61,6 +61,7 @@ struct qzd_ctx {
     uint32_t *d_cdesc; size_t cdesc_cap;            /* per-slot descriptors of a coalesced launch (qzd_deflate_slots); capacity in bytes */
     uint8_t *d_lane; size_t lane_cap;               /* device-only scratch of the lane, wide, lazy and LZ4-HC compress paths (carve_symbols) */
     float inf_ms[4];
+    int lz4d_route;                 /* qzd_lz4_decode_route: 0 auto, 1 a wave per frame, 2 a wave per block wherever a frame qualifies */
     bool no_stream_in;              /* this call is the batched retry of a launch that gave up waiting for its input */
     /* device arrays of the last two-phase inflate (phase A done, phase B still to run): two_phase() / two_phase_resolve() */
     struct { void *segs, *res, *ts, *lits, *seqs, *chains; uint32_t *ord; uint32_t nsegs, K; } tp;

@@ -1002,7 +1002,8 @@ QZ_DEV int qzk_l4_window(qzk_l4p *P, int lane)
     return 0;
 }
 
-/* decode one block through S (history = the frame's output so far: linked frames).  0 or an error */
+/* decode one block through S (a match may reach back to S->o: the frame's first byte in a linked frame, the block's own in
+ * an independent one).  0, QZK_LZ4_EOUT (the block's output does not fit S->out_cap) or -1 */
 QZ_DEV int qzk_lz4_dblock(qzk_rb *S, const uint8_t *blk, uint32_t n, uint32_t lim, uint8_t *ring, qzk_l4rec *queue, int lane)
 {
     if (n == 0) return -1;
@@ -1021,7 +1022,7 @@ QZ_DEV int qzk_lz4_dblock(qzk_rb *S, const uint8_t *blk, uint32_t n, uint32_t li
         if (fit == 0) {
             /* one sequence that is more than a batch holds: straight to the output */
             const uint32_t gL = qz_readlane(r.lit, 0), gM = qz_readlane(r.ml, 0), gD = qz_readlane(r.off, 0);
-            if ((uint64_t)S->obase + gL + gM > S->out_cap) return -1;
+            if ((uint64_t)S->obase + gL + gM > S->out_cap) return QZK_LZ4_EOUT;
             if (gM != 0 && (uint64_t)gD > (uint64_t)S->obase + gL) return -1;
             qzk_rb_flush(S, lane);
             qzk_rb_direct(S, blk + span0, gL, lane);
@@ -1033,12 +1034,18 @@ QZ_DEV int qzk_lz4_dblock(qzk_rb *S, const uint8_t *blk, uint32_t n, uint32_t li
         }
         if ((uint32_t)lane >= fit) { s_tot -= r.lit + r.ml; r.lit = 0; r.ml = 0; }
         const uint32_t Tb = qz_readlane(s_tot, (int)fit - 1), span_len = qz_readlane(s_span, (int)fit - 1);
-        if (qzk_rb_batch(S, blk + span0, span_len, r.lit_off - span0, r.lit, r.ml, r.off, s_tot, Tb, lane)) return -1;
+        const int e = qzk_rb_batch(S, blk + span0, span_len, r.lit_off - span0, r.lit, r.ml, r.off, s_tot, Tb, lane);
+        if (e) return e == -2 ? QZK_LZ4_EOUT : -1;
         P.qh += fit;
     }
     return 0;
 }
 
+/* One wave per frame, any block mode: the route of every frame below QZK_LZ4_CAND bytes, of linked frames and of whatever
+ * the plan kernel below does not take.  Block checksums (FLG bit 4) are verified before a block is decoded, as liblz4 does
+ * (blockChecksum_invalid) - the hash is staged in the sequence queue, which is empty between blocks.  In a frame of
+ * independent blocks (FLG bit 5) the window starts afresh at every block's first byte: a match that reaches in front of
+ * its block is a data error there (LZ4F_decompress: decompressionFailed), and no block decodes to more than the BD maximum. */
 QZ_KERNEL_OCC(64, 6) qzk_lz4d_kernel(const uint8_t *comp, uint8_t *out, const qzk_lz4seg *segs, qzk_lz4res *res, uint32_t nsegs)
 {
     QZ_LDS __attribute__((aligned(16))) uint8_t obuf[QZK_RB_OB];
@@ -1053,6 +1060,7 @@ QZ_KERNEL_OCC(64, 6) qzk_lz4d_kernel(const uint8_t *comp, uint8_t *out, const qz
     uint8_t *o = out + sg.out_off;
     const uint32_t n = sg.in_len;
     int status = QZK_LZ4_EDATA; uint32_t pos = 0;
+    uint32_t done = 0;                                              /* independent blocks: the output of the blocks before S's */
     qzk_rb S;
     qzk_rb_init(&S, obuf, lbuf, o, 0, sg.out_cap);
     do {
@@ -1060,7 +1068,7 @@ QZ_KERNEL_OCC(64, 6) qzk_lz4d_kernel(const uint8_t *comp, uint8_t *out, const qz
         if (qz_ld32(p) != 0x184D2204u) break;
         uint32_t flg = p[4];
         if ((flg >> 6) != 1 || (flg & 2)) break;
-        const bool bcheck = (flg >> 4) & 1, csize = (flg >> 3) & 1, ccheck = (flg >> 2) & 1, dict = flg & 1;
+        const bool indep = (flg >> 5) & 1, bcheck = (flg >> 4) & 1, csize = (flg >> 3) & 1, ccheck = (flg >> 2) & 1, dict = flg & 1;
         /* BD: the frame's largest block (64 KB << 2 (id - 4), id 4..7: 4 MiB at most).  liblz4 refuses a block above it
          * (LZ4F_decompress: maxBlockSizeInvalid / "block size > maxBlockSize"), and so must this decoder: the walk below adds
          * sequence lengths in 32 bits, and only a block of 16 MiB and more could make such a sum wrap */
@@ -1071,6 +1079,7 @@ QZ_KERNEL_OCC(64, 6) qzk_lz4d_kernel(const uint8_t *comp, uint8_t *out, const qz
         if (pos + 1 > n) { status = QZK_LZ4_EIN; break; }
         if (p[pos] != ((qzk_wave_xxh32(p + 4, pos - 4, lane) >> 8) & 0xff)) break;
         pos++;
+        if (indep && bmax < S.out_cap) S.out_cap = bmax;
         bool ok = true;
         for (;;) {
             if (pos + 4 > n) { status = QZK_LZ4_EIN; ok = false; break; }
@@ -1079,13 +1088,29 @@ QZ_KERNEL_OCC(64, 6) qzk_lz4d_kernel(const uint8_t *comp, uint8_t *out, const qz
             uint32_t bsz = bh & 0x7fffffffu;
             if (bsz > bmax) { ok = false; break; }
             if (bsz > n - pos) { status = QZK_LZ4_EIN; ok = false; break; }
+            if (bcheck) {
+                if (n - pos - bsz < 4) { status = QZK_LZ4_EIN; ok = false; break; }
+                const uint32_t h = qzk_wave_xxh32_staged(p + pos, bsz, (uint8_t *)queue, lane);
+                qz_lds_sync();
+                if (qz_ld32(p + pos + bsz) != h) { ok = false; break; }
+            }
+            if (indep && S.obase) {                                 /* the window afresh at this block's first byte */
+                qzk_rb_flush(&S, lane);
+                done += S.obase;
+                const uint32_t left = sg.out_cap - done;
+                qzk_rb_init(&S, obuf, lbuf, o + done, 0, left < bmax ? left : bmax);
+            }
             if (bh & 0x80000000u) {
-                if (bsz > sg.out_cap - S.obase) { status = QZK_LZ4_EOUT; ok = false; break; }
+                if (bsz > S.out_cap - S.obase) { status = QZK_LZ4_EOUT; ok = false; break; }
                 qzk_rb_flush(&S, lane);
                 qzk_rb_direct(&S, p + pos, bsz, lane);
                 qz_wave_sync();
                 qzk_rb_skip(&S, bsz);
-            } else if (qzk_lz4_dblock(&S, p + pos, bsz, n - pos, ring, queue, lane)) { ok = false; break; }
+            } else {
+                const int e = qzk_lz4_dblock(&S, p + pos, bsz, n - pos, ring, queue, lane);
+                /* (what does not fit the BD maximum of an independent block is bad data; what does not fit the caller's room is not) */
+                if (e) { if (e == QZK_LZ4_EOUT && S.out_cap == sg.out_cap - done) status = QZK_LZ4_EOUT; ok = false; break; }
+            }
             pos += bsz + (bcheck ? 4 : 0);
         }
         qzk_rb_flush(&S, lane);
@@ -1093,12 +1118,208 @@ QZ_KERNEL_OCC(64, 6) qzk_lz4d_kernel(const uint8_t *comp, uint8_t *out, const qz
         if (ccheck) {
             if (pos + 4 > n) { status = QZK_LZ4_EIN; break; }
             qz_wave_sync();
-            if (qz_ld32(p + pos) != qzk_wave_xxh32_staged(o, S.obase, obuf, lane)) break;
+            if (qz_ld32(p + pos) != qzk_wave_xxh32_staged(o, done + S.obase, obuf, lane)) break;
             pos += 4;
         }
         status = QZK_LZ4_OK;
     } while (0);
-    if (lane == 0) { qzk_lz4res r; r.status = status; r.in_used = pos; r.out_len = S.obase; r.pad = 0; res[s] = r; }
+    if (lane == 0) { qzk_lz4res r; r.status = status; r.in_used = pos; r.out_len = done + S.obase; r.pad = 0; res[s] = r; }
+}
+
+/* ------------------------------------------------------------------ K5b: a frame of independent blocks, a wave per block
+ * A frame with FLG bit 5 names its own parallelism: block words delimit the blocks and no block reads another's output.
+ * The stock lz4 tool writes a whole file as ONE such frame (4 MiB blocks), streaming writers flush many short blocks into
+ * one; on qzk_lz4d_kernel they are one wave's serial work.  Here, for the frames of a call above QZK_LZ4_CAND bytes:
+ *   plan    a wave per candidate frame: the header checks of qzk_lz4d_kernel, then hop from block word to block word and
+ *           note every block in the frame's share of a table; frames that do not qualify are left to qzk_lz4d_kernel
+ *   size    a wave per block: XXH32 of the body against the block checksum; the decoded length by the token walk alone
+ *   scan    a wave per frame: every block's place in the frame's output, the frame's total against out_cap - a frame that
+ *           does not fit is refused before a byte of it is written
+ *   block   a wave per block: qzk_lz4_dblock into a window of its own at the block's place, out_cap = its decoded length
+ *   finish  a wave per frame: XXH32 of the content (serial - there is no parallel XXH32), the result record
+ * Neighbouring blocks share 16-byte rows of the output wherever a block's length is no multiple of 16.  The engine never
+ * reads a row of the output in order to store it: a window's first and last row leave under a byte mask (qzk_rb_batch's
+ * `hd` lanes, qzk_rb_flush), everything between is whole rows inside the block's own bytes, and the direct paths store
+ * exact byte ranges - so two waves never write the same byte and never rewrite each other's. */
+#define QZK_LZ4_CAND 65571u         /* the largest frame of ONE 64 KB block: 19 header, 4 word, 65536 body, 4 block checksum, 4 end mark, 4 content checksum */
+#define QZK_LZ4_SHARE(in_len) ((in_len) / 1024u + 64u)             /* table entries a candidate frame may fill */
+#define QZK_LZ4P_WAVE 0             /* plan verdicts: the frame goes to qzk_lz4d_kernel, */
+#define QZK_LZ4P_BLOCKS 1           /* its blocks stand in the table, */
+#define QZK_LZ4P_DONE 2             /* it is malformed at the level of the block words and has its result */
+typedef struct { uint32_t seg, body, len, chk; } qzk_lz4blk;       /* body, chk: offsets in the frame (chk 0: no block checksum); len bit 31: stored */
+typedef struct { uint32_t seg, first, cap, pad; } qzk_lz4cand;     /* a candidate's share of the table */
+typedef struct { int32_t route; uint32_t nblk, end, flags; } qzk_lz4plan;  /* end: behind the end mark; flags: bit 0 content checksum, bits 4-6 block id */
+typedef struct { uint32_t seg, first, nblk, wbase, end, flags; int32_t status; uint32_t total; } qzk_lz4fr;    /* wbase: the frame's first wave in the block launches */
+
+QZ_KERNEL_MAX(64) qzk_lz4d_plan_kernel(const uint8_t *comp, const qzk_lz4seg *segs, const qzk_lz4cand *cand, uint32_t ncand,
+                                       uint32_t minblk, qzk_lz4blk *table, qzk_lz4plan *plan, qzk_lz4res *res)
+{
+    const int lane = qz_lane();
+    const uint32_t c = blockIdx.x;
+    if (c >= ncand) return;
+    const qzk_lz4cand cd = cand[c];
+    const qzk_lz4seg sg = segs[cd.seg];
+    const uint8_t *p = comp + sg.in_off;
+    const uint32_t n = sg.in_len;
+    int status = QZK_LZ4_EDATA, route = QZK_LZ4P_DONE; uint32_t pos = 0, nblk = 0, flags = 0;
+    do {
+        if (n < 7) { status = QZK_LZ4_EIN; break; }
+        if (qz_ld32(p) != 0x184D2204u) break;
+        const uint32_t flg = p[4];
+        if ((flg >> 6) != 1 || (flg & 2)) break;
+        const bool indep = (flg >> 5) & 1, bcheck = (flg >> 4) & 1, csize = (flg >> 3) & 1, ccheck = (flg >> 2) & 1, dict = flg & 1;
+        const uint32_t bd = p[5], bid = (bd >> 4) & 7;
+        if ((bd & 0x8f) || bid < 4) break;
+        const uint32_t bmax = 65536u << (2 * (bid - 4));
+        pos = 6 + (csize ? 8 : 0) + (dict ? 4 : 0);
+        if (pos + 1 > n) { status = QZK_LZ4_EIN; break; }
+        if (p[pos] != ((qzk_wave_xxh32(p + 4, pos - 4, lane) >> 8) & 0xff)) break;
+        pos++;
+        if (!indep) { route = QZK_LZ4P_WAVE; break; }
+        flags = (ccheck ? 1u : 0u) | bid << 4;
+        bool ok = true;
+        for (;;) {                                                  /* wave-uniform: one serial hop per block */
+            if (pos + 4 > n) { status = QZK_LZ4_EIN; ok = false; break; }
+            const uint32_t bh = qz_ld32(p + pos); pos += 4;
+            if (bh == 0) break;
+            const uint32_t bsz = bh & 0x7fffffffu;
+            if (bsz > bmax) { ok = false; break; }
+            if (bsz > n - pos || (bcheck && n - pos - bsz < 4)) { status = QZK_LZ4_EIN; ok = false; break; }
+            if (nblk < cd.cap && lane == 0) {
+                qzk_lz4blk b; b.seg = cd.seg; b.body = pos; b.len = bh; b.chk = bcheck ? pos + bsz : 0;
+                table[cd.first + nblk] = b;
+            }
+            nblk++;
+            pos += bsz + (bcheck ? 4 : 0);
+        }
+        if (!ok) break;
+        if (ccheck && pos + 4 > n) { status = QZK_LZ4_EIN; break; }
+        route = (nblk < minblk || nblk > cd.cap) ? QZK_LZ4P_WAVE : QZK_LZ4P_BLOCKS;
+    } while (0);
+    if (lane == 0) {
+        qzk_lz4plan pl; pl.route = route; pl.nblk = nblk; pl.end = pos; pl.flags = flags; plan[c] = pl;
+        if (route == QZK_LZ4P_DONE) { qzk_lz4res r; r.status = status; r.in_used = pos; r.out_len = 0; r.pad = 0; res[cd.seg] = r; }
+    }
+}
+
+/* the frame of wave w of a block launch: the last one whose wbase is <= w (wave-uniform) */
+QZ_DEV uint32_t qzk_lz4_frame_of(const qzk_lz4fr *fr, uint32_t nfr, uint32_t w)
+{
+    uint32_t lo = 0, hi = nfr;
+    while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (fr[mid].wbase <= w) lo = mid; else hi = mid; }
+    return lo;
+}
+
+/* what a block decodes to, by qzk_lz4_dblock's walk without its copies.  0, or -1: not a block, or more than cap bytes */
+QZ_DEV int qzk_lz4_dsize(const uint8_t *blk, uint32_t n, uint32_t lim, uint8_t *ring, qzk_l4rec *queue, uint32_t cap, uint32_t *len, int lane)
+{
+    if (n == 0) return -1;
+    qzk_l4p P; P.blk = blk; P.n = n; P.lim = lim; P.ring = ring; P.q = queue; P.filled = 0; P.qh = P.qt = 0; P.s = 0;
+    P.pre = qzk_l4_fetch(&P, 0, lane);
+    uint32_t tot = 0;                                               /* (n <= 4 MiB: every stream byte adds 255 at most) */
+    while (P.s < n) {
+        if (qzk_l4_window(&P, lane)) return -1;
+        uint32_t mine = 0;                                          /* a window queues at most 65 records */
+        for (uint32_t i = P.qh + (uint32_t)lane; i < P.qt; i += 64) { const qzk_l4rec r = P.q[i & (QZK_L4_Q - 1)]; mine += r.lit + r.ml; }
+        tot += qz_readlane(qz_wave_incl_scan(mine), 63);
+        P.qh = P.qt;
+        if (tot > cap) return -1;
+    }
+    *len = tot;
+    return 0;
+}
+
+QZ_KERNEL_OCC(64, 6) qzk_lz4d_size_kernel(const uint8_t *comp, const qzk_lz4seg *segs, const qzk_lz4blk *table, qzk_lz4fr *fr,
+                                          uint32_t nfr, uint32_t nw, uint32_t *dlen)
+{
+    QZ_LDS __attribute__((aligned(16))) uint8_t ring[QZK_L4_RING + 16];
+    QZ_LDS qzk_l4rec queue[QZK_L4_Q];                               /* the hash's staging too */
+    const int lane = qz_lane();
+    const uint32_t w = blockIdx.x;
+    if (w >= nw) return;
+    const uint32_t f = qzk_lz4_frame_of(fr, nfr, w);
+    const uint32_t slot = fr[f].first + (w - fr[f].wbase);
+    const qzk_lz4blk b = table[slot];
+    const qzk_lz4seg sg = segs[b.seg];
+    const uint8_t *p = comp + sg.in_off;
+    const uint32_t len = b.len & 0x7fffffffu, bmax = 65536u << (2 * (((fr[f].flags >> 4) & 7) - 4));
+    bool bad = false;
+    uint32_t d = len;
+    if (b.chk) {
+        const uint32_t h = qzk_wave_xxh32_staged(p + b.body, len, (uint8_t *)queue, lane);
+        qz_lds_sync();
+        bad = qz_ld32(p + b.chk) != h;
+    }
+    if (!bad && !(b.len >> 31)) bad = qzk_lz4_dsize(p + b.body, len, sg.in_len - b.body, ring, queue, bmax, &d, lane) != 0;
+    if (lane == 0) {
+        dlen[slot] = bad ? 0u : d;
+        if (bad) fr[f].status = QZK_LZ4_EDATA;                      /* (every wave that writes it writes the same) */
+    }
+}
+
+QZ_KERNEL_MAX(64) qzk_lz4d_scan_kernel(const qzk_lz4seg *segs, qzk_lz4fr *fr, uint32_t nfr, const uint32_t *dlen, uint32_t *ooff)
+{
+    const int lane = qz_lane();
+    const uint32_t f = blockIdx.x;
+    if (f >= nfr) return;
+    const qzk_lz4fr F = fr[f];
+    if (F.status) return;
+    const uint32_t cap = segs[F.seg].out_cap;
+    uint64_t run = 0;
+    for (uint32_t i0 = 0; i0 < F.nblk && run <= cap; i0 += 64) {
+        const uint32_t i = i0 + (uint32_t)lane, v = i < F.nblk ? dlen[F.first + i] : 0u;
+        const uint32_t inc = qz_wave_incl_scan(v);                  /* 64 blocks of 4 MiB at most */
+        if (i < F.nblk) ooff[F.first + i] = (uint32_t)run + inc - v;    /* (used only if the whole frame fits: no wrap then) */
+        run += qz_readlane(inc, 63);
+    }
+    if (lane == 0) {
+        fr[f].total = run > cap ? 0u : (uint32_t)run;
+        if (run > cap) fr[f].status = QZK_LZ4_EOUT;
+    }
+}
+
+QZ_KERNEL_OCC(64, 6) qzk_lz4d_block_kernel(const uint8_t *comp, uint8_t *out, const qzk_lz4seg *segs, const qzk_lz4blk *table,
+                                           qzk_lz4fr *fr, uint32_t nfr, uint32_t nw, const uint32_t *dlen, const uint32_t *ooff)
+{
+    QZ_LDS __attribute__((aligned(16))) uint8_t obuf[QZK_RB_OB];
+    QZ_LDS __attribute__((aligned(16))) uint8_t lbuf[QZK_RB_LT];
+    QZ_LDS __attribute__((aligned(16))) uint8_t ring[QZK_L4_RING + 16];
+    QZ_LDS qzk_l4rec queue[QZK_L4_Q];
+    const int lane = qz_lane();
+    const uint32_t w = blockIdx.x;
+    if (w >= nw) return;
+    const uint32_t f = qzk_lz4_frame_of(fr, nfr, w);
+    if (fr[f].status) return;                                       /* (set by the size or the scan kernel: nothing of the frame is written) */
+    const uint32_t slot = fr[f].first + (w - fr[f].wbase);
+    const qzk_lz4blk b = table[slot];
+    const qzk_lz4seg sg = segs[b.seg];
+    const uint8_t *p = comp + sg.in_off;
+    const uint32_t len = b.len & 0x7fffffffu, d = dlen[slot];
+    if (d == 0) return;
+    qzk_rb S;
+    qzk_rb_init(&S, obuf, lbuf, out + sg.out_off + ooff[slot], 0, d);  /* no history, and not a byte beyond the block's own */
+    if (b.len >> 31) { qzk_rb_direct(&S, p + b.body, len, lane); return; }
+    const int e = qzk_lz4_dblock(&S, p + b.body, len, sg.in_len - b.body, ring, queue, lane);
+    qzk_rb_flush(&S, lane);
+    if ((e || S.obase != d) && lane == 0) fr[f].status = QZK_LZ4_EDATA;     /* a match that reaches in front of the block */
+}
+
+QZ_KERNEL_MAX(64) qzk_lz4d_finish_kernel(const uint8_t *comp, const uint8_t *out, const qzk_lz4seg *segs, const qzk_lz4fr *fr,
+                                         uint32_t nfr, qzk_lz4res *res)
+{
+    QZ_LDS __attribute__((aligned(16))) uint8_t stage[2048];
+    const int lane = qz_lane();
+    const uint32_t f = blockIdx.x;
+    if (f >= nfr) return;
+    const qzk_lz4fr F = fr[f];
+    const qzk_lz4seg sg = segs[F.seg];
+    int status = F.status;
+    uint32_t used = F.end;
+    if (F.flags & 1) {
+        if (!status && qz_ld32(comp + sg.in_off + F.end) != qzk_wave_xxh32_staged(out + sg.out_off, F.total, stage, lane)) status = QZK_LZ4_EDATA;
+        used += 4;
+    }
+    if (lane == 0) { qzk_lz4res r; r.status = status; r.in_used = used; r.out_len = status ? 0u : F.total; r.pad = 0; res[F.seg] = r; }
 }
 
 #endif
