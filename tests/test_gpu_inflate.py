@@ -219,3 +219,52 @@ def test_marker_scan_finds_what_the_reference_scan_finds(ctx, monkeypatch):
     assert rc == 0
     iu, out, crc = _inflate(ctx, comp, len(src), 65536)
     assert out == src and iu == len(comp)
+
+
+def test_piecewise_decode_from_host_through_the_device_abi(ctx, monkeypatch):
+    """qzd_inflate_stream_from_host on a member small enough for every run of the suite (qzDecompress takes that route from
+    24 MiB of compressed bytes on): 2 MiB in 128 segments of 16 KB, cut into three pieces, so that every piece holds tens of
+    segments and the chain's state crosses two piece boundaries; pageable buffers on both sides.  A damaged member and a
+    destination too small abandon the pieces and must end exactly as qzd_inflate_stream ends for the same bytes."""
+    import ctypes as C
+    L = ctx.L
+    vp = C.c_void_p
+    L.qzd_inflate_stream_from_host.restype = C.c_int
+    L.qzd_inflate_stream_from_host.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64),
+                                               C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), vp, C.POINTER(C.c_int)]
+    n, hint = 2 << 20, 16384
+    src = datagen.gen_bytes("silesia", n, 53)
+    rc, _, comp, _ = O.sw_compress("RAW", src, hint, 1, cap=n * 9 // 8 + 65536)
+    assert rc == 0 and comp.count(b"\x00\x00\xff\xff") >= n // hint - 1
+    want_crc = zlib.crc32(src) & 0xffffffff
+    d_src = ctx.alloc(len(comp)); d_dst = ctx.alloc(n)
+
+    def from_host(data, dst_cap):
+        h_src = np.frombuffer(data, dtype=np.uint8).copy()
+        h_dst = np.zeros(n, np.uint8)
+        iu, ol, crc, sent = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0), C.c_int(-1)
+        rc = L.qzd_inflate_stream_from_host(ctx.h, h_src.ctypes.data, len(data), d_src.ptr, d_dst.ptr, dst_cap, hint,
+                                            C.byref(iu), C.byref(ol), C.byref(crc), h_dst.ctypes.data, C.byref(sent))
+        return rc, iu.value, ol.value, crc.value, sent.value, h_dst
+
+    def on_device(nbytes, dst_cap):                 # the same bytes, which from_host left at d_src
+        iu, ol, crc = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+        rc = L.qzd_inflate_stream(ctx.h, d_src.ptr, nbytes, d_dst.ptr, dst_cap, hint, C.byref(iu), C.byref(ol), C.byref(crc))
+        return rc, iu.value, ol.value
+
+    try:
+        monkeypatch.setenv("QATZIP_AMD_PIPE", "3")
+        for cuts in (None, "1,2"):                  # thirds; a first piece of 20 KiB that holds candidate 0 alone - the next piece's
+            if cuts:
+                monkeypatch.setenv("QATZIP_AMD_PIPE_CUTS", cuts)
+            rc, iu, ol, crc, sent, h_dst = from_host(comp, n)
+            assert (rc, iu, ol, crc, sent) == (0, len(comp), n, want_crc, 1), cuts
+            assert h_dst.tobytes() == src, cuts
+        monkeypatch.delenv("QATZIP_AMD_PIPE_CUTS")
+        bad = bytearray(comp); bad[len(bad) // 2] ^= 0x10
+        rc, iu, ol, crc, sent, h_dst = from_host(bytes(bad), n)
+        assert (rc, iu, ol) == on_device(len(bad), n)
+        rc, iu, ol, crc, sent, h_dst = from_host(comp, 5000)
+        assert rc == -3 and sent == 0               # QZD_ERR_DSTCAP
+    finally:
+        d_src.free(); d_dst.free()
