@@ -174,6 +174,55 @@ uint32_t qzd_adler32_combine(uint32_t adler1, uint32_t adler2, uint64_t len2);
 int qzd_crc32(qzd_ctx *ctx, const uint8_t *d_data, uint64_t n, uint32_t *h_crc);
 int qzd_crc32_ranges(qzd_ctx *ctx, const uint8_t *d_data, const void *h_ranges, uint32_t nranges, uint32_t *h_crc);
 
+/* ------------------------------------------------------------------ block-addressable compression
+ *
+ * What qzCompressWithMetadataExt / qzDecompressWithMetadataExt and the Crc64 calls of include/qatzip.h stand on: a buffer
+ * as independent blocks with a table beside the data, and CRCs under a caller's polynomial.
+ *
+ * qzd_crccfg is the Rocksoft model of a CRC (QzCrc64Config_T / QzCrc32Config_T, include/qatzip.h): polynomial without its
+ * top term, initial register, reflect_in / reflect_out 0 or 1, xor_out; for width 32 the 64-bit fields hold 32-bit values.
+ * {0x04C11DB7, 0xFFFFFFFF, 1, 1, 0xFFFFFFFF} is zlib's crc32(), {0x42F0E1EBA9EA3693, 0, 0, 0, 0} CRC-64/ECMA-182. */
+typedef struct { uint64_t polynomial, initial_value; uint32_t reflect_in, reflect_out; uint64_t xor_out; } qzd_crccfg;
+
+/* CRC (width 32 or 64, polynomial with bit 0 set) of nranges ranges (qzd_range) of HBM-resident data, one launch, a workgroup
+ * a range.  h_start (optional): per range the finalised CRC of the bytes before it, as zlib's crc32() chains - NULL starts
+ * every range as a new message.  h_out <- the finalised CRCs, 64 bits each whatever the width. */
+int qzd_crcn_ranges(qzd_ctx *ctx, const uint8_t *d_data, const void *h_ranges, uint32_t nranges, int width,
+                    const qzd_crccfg *cfg, const uint64_t *h_start, uint64_t *h_out);
+/* XXH32 (seed 0) of nranges ranges, one launch, a wave a range */
+int qzd_xxh32_ranges(qzd_ctx *ctx, const uint8_t *d_data, const void *h_ranges, uint32_t nranges, uint32_t *h_hash);
+
+/* one block of a block call: where it stands in the destination, its bytes there, flags 1 = a raw-deflate stream / 0 = the
+ * plaintext itself, XXH32 of the plaintext, and the CRCs of the plaintext (in_) and of the bytes in the destination (out_)
+ * under the 32- and the 64-bit config */
+typedef struct { uint64_t offset; uint32_t size, flags, hash, in_crc32, out_crc32, pad; uint64_t in_crc64, out_crc64; } qzd_blockrec;
+
+/* The n bytes at d_src as ceil(n / block_sz) independent blocks: block k is the raw-deflate stream of its block_sz bytes
+ * alone, closed with BFINAL, at zlib level `level` (one qzd_deflate_slots launch) - unless that stream is longer than
+ * thrshold bytes, then the plaintext is stored in its place.  The blocks are written back to back to d_dst from block 0;
+ * h_records gets one record per block.  Hash, the four CRCs, the choice, the scan of the sizes and the gather all happen
+ * on the device, in a number of launches that does not depend on the number of blocks.  cfg32 / cfg64: NULL = zlib's
+ * CRC-32 / CRC-64/ECMA-182.  d_src must be readable for a whole number of blocks (as qzd_deflate_slots' slots).
+ *   h_out_len <- bytes written
+ * QZD_ERR_DSTCAP: dst_cap does not hold every block; the leading blocks that fit whole were written, *h_out_len counts
+ * them, the records of all blocks are valid but out_crc32 / out_crc64 of the unwritten ones are those of no bytes. */
+int qzd_blocks_compress(qzd_ctx *ctx, const uint8_t *d_src, uint64_t n, uint32_t block_sz, int level, uint32_t thrshold,
+                        const qzd_crccfg *cfg32, const qzd_crccfg *cfg64, uint8_t *d_dst, uint64_t dst_cap,
+                        qzd_blockrec *h_records, uint64_t *h_out_len);
+
+/* The reverse, from the table: block k (offset, size, flags, hash of h_records[k]; the CRC fields are not read) is taken
+ * from d_comp + offset and its plaintext goes to d_out + k * block_sz - stored blocks by a copy kernel, compressed ones
+ * as segments of one qzd_inflate_segments call - then every block's XXH32 is checked.  The offsets need not be in order
+ * nor back to back: a table of one record decodes that block alone.
+ *   h_status (optional) <- per block 0, or -1 data (bad stream, stream not ending at `size`, a block but the last not
+ *                          block_sz bytes, wrong hash), -2 output capacity, -3 record outside comp_len / larger than a block
+ *   h_out_len <- (nblocks - 1) * block_sz + the last block's bytes
+ * Returns QZD_ERR_DSTCAP when out_cap cannot hold the output (nothing is decoded when that is known from the table),
+ * else QZD_ERR_DATA when any block failed. */
+int qzd_blocks_decompress(qzd_ctx *ctx, const uint8_t *d_comp, uint64_t comp_len, const qzd_blockrec *h_records,
+                          uint32_t nblocks, uint32_t block_sz, uint8_t *d_out, uint64_t out_cap, int32_t *h_status,
+                          uint64_t *h_out_len);
+
 /* ------------------------------------------------------------------ LZ4 frames
  * qzd_lz4seg { u64 in_off; u64 out_off; u32 in_len; u32 out_cap; }
  * qzd_lz4res { i32 status; u32 in_used; u32 out_len; u32 pad; }   status 0 ok, -1 data, -2 capacity, -3 truncated */

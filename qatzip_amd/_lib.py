@@ -17,6 +17,12 @@ class QzdError(RuntimeError):
     pass
 
 
+class CrcCfg(C.Structure):
+    """qzd_crccfg: a CRC in the Rocksoft model (width 32: the 64-bit fields hold 32-bit values)"""
+    _fields_ = [("polynomial", C.c_uint64), ("initial_value", C.c_uint64), ("reflect_in", C.c_uint32),
+                ("reflect_out", C.c_uint32), ("xor_out", C.c_uint64)]
+
+
 def load(build_if_missing=True):
     global _lib
     if _lib is not None:
@@ -82,6 +88,11 @@ def load(build_if_missing=True):
     L.qzd_pcie_peak.argtypes = [vp, C.c_uint64, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.qzd_crc32_fold.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint64]; L.qzd_crc32_fold.restype = C.c_uint32
     L.qzd_crc32_combine.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64]; L.qzd_crc32_combine.restype = C.c_uint32
+    L.qzd_crcn_ranges.argtypes = [vp, u8p, vp, C.c_uint32, C.c_int, C.POINTER(CrcCfg), vp, vp]
+    L.qzd_xxh32_ranges.argtypes = [vp, u8p, vp, C.c_uint32, vp]
+    L.qzd_blocks_compress.argtypes = [vp, u8p, C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, C.POINTER(CrcCfg), C.POINTER(CrcCfg),
+                                      u8p, C.c_uint64, vp, C.POINTER(C.c_uint64)]
+    L.qzd_blocks_decompress.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint32, C.c_uint32, u8p, C.c_uint64, vp, C.POINTER(C.c_uint64)]
     _lib = L
     return L
 
@@ -91,6 +102,9 @@ SEG_DT = np.dtype([("in_off", "<u8"), ("out_off", "<u8"), ("in_len", "<u4"), ("o
 RES_DT = np.dtype([("status", "<i4"), ("in_used", "<u4"), ("out_len", "<u4"), ("nblocks", "<u4")])
 LZ4SEG_DT = np.dtype([("in_off", "<u8"), ("out_off", "<u8"), ("in_len", "<u4"), ("out_cap", "<u4")])
 LZ4RES_DT = np.dtype([("status", "<i4"), ("in_used", "<u4"), ("out_len", "<u4"), ("pad", "<u4")])
+RANGE_DT = np.dtype([("off", "<u8"), ("len", "<u4"), ("pad", "<u4")])
+BLOCKREC_DT = np.dtype([("offset", "<u8"), ("size", "<u4"), ("flags", "<u4"), ("hash", "<u4"), ("in_crc32", "<u4"),
+                        ("out_crc32", "<u4"), ("pad", "<u4"), ("in_crc64", "<u8"), ("out_crc64", "<u8")])
 
 
 def exported_symbols():
@@ -104,6 +118,7 @@ def exported_symbols():
             "qzd_deflate_slots", "qzd_inflate_stream_to_host", "qzd_inflate_stream_from_host", "qzamd_async_stats", "qzd_shard_root_create",
             "qzd_shard_attach", "qzd_shard_slot_handle", "qzd_shard_attach_slot", "qzd_lz4_compress_linked", "qzd_shard_put", "qzd_shard_finish", "qzd_shard_close", "qzd_crc32_combine",
             "qzd_lz4hc_compress_frames", "qzd_lz4hc_compress_frames_hw", "qzd_lz4hc_compress_linked",
+            "qzd_crcn_ranges", "qzd_xxh32_ranges", "qzd_blocks_compress", "qzd_blocks_decompress",
             "qzd_crc32_fold", "qzd_pcie_peak", "qzd_rccl_unique_id", "qzd_rccl_create", "qzd_rccl_gather", "qzd_rccl_close"]
 
 
@@ -235,6 +250,44 @@ class Context:
         crc = C.c_uint32(0)
         self._chk(self.L.qzd_crc32(self.h, d_data.ptr, n, C.byref(crc)))
         return crc.value
+
+    # -- block-addressable compression
+    def crcn_ranges(self, d_data, ranges, width, cfg, start=None):
+        """ranges: list of (off, len); cfg: (polynomial, initial_value, reflect_in, reflect_out, xor_out); start: per range the
+        finalised CRC of the bytes before it -> array of finalised CRCs"""
+        ra = np.array([(o, n, 0) for o, n in ranges], dtype=RANGE_DT)
+        out = np.zeros(len(ranges), np.uint64)
+        st = None if start is None else np.array(start, np.uint64)
+        self._chk(self.L.qzd_crcn_ranges(self.h, d_data.ptr, ra.ctypes.data, len(ranges), width, C.byref(CrcCfg(*cfg)),
+                                         None if st is None else st.ctypes.data, out.ctypes.data))
+        return out
+
+    def xxh32_ranges(self, d_data, ranges):
+        ra = np.array([(o, n, 0) for o, n in ranges], dtype=RANGE_DT)
+        out = np.zeros(len(ranges), np.uint32)
+        self._chk(self.L.qzd_xxh32_ranges(self.h, d_data.ptr, ra.ctypes.data, len(ranges), out.ctypes.data))
+        return out
+
+    def blocks_compress(self, d_src, n, block_sz, level, thrshold, d_dst, dst_cap=None, cfg32=None, cfg64=None):
+        """-> (rc, out_len, records): rc 0, or QZD_ERR_DSTCAP (-3) with the leading blocks that fit; other codes raise"""
+        nb = (n + block_sz - 1) // block_sz
+        recs = np.zeros(nb, BLOCKREC_DT)
+        ol = C.c_uint64(0)
+        rc = self.L.qzd_blocks_compress(self.h, d_src.ptr, n, block_sz, level, thrshold,
+                                        C.byref(CrcCfg(*cfg32)) if cfg32 else None, C.byref(CrcCfg(*cfg64)) if cfg64 else None,
+                                        d_dst.ptr, d_dst.nbytes if dst_cap is None else dst_cap, recs.ctypes.data, C.byref(ol))
+        if rc not in (0, -3):
+            self._chk(rc)
+        return rc, ol.value, recs
+
+    def blocks_decompress(self, d_comp, comp_len, recs, block_sz, d_out, out_cap=None):
+        """-> (rc, out_len, per-block status)"""
+        recs = np.ascontiguousarray(recs, dtype=BLOCKREC_DT)
+        status = np.zeros(len(recs), np.int32)
+        ol = C.c_uint64(0)
+        rc = self.L.qzd_blocks_decompress(self.h, d_comp.ptr, comp_len, recs.ctypes.data, len(recs), block_sz, d_out.ptr,
+                                          d_out.nbytes if out_cap is None else out_cap, status.ctypes.data, C.byref(ol))
+        return rc, ol.value, status
 
     # -- LZ4
     def lz4_compress_frames(self, d_src, n, d_dst, frame_sz=65536, level=1, hw=False):

@@ -8,6 +8,7 @@ from ._lib import load
 
 QZ_OK, QZ_DUPLICATE, QZ_PARAMS, QZ_FAIL, QZ_BUF_ERROR, QZ_DATA_ERROR = 0, 1, -1, -2, -3, -4
 QZ_NOT_SUPPORTED, QZ_NOSW_NO_HW, QZ_UNSUPPORTED_FMT = -200, -101, 16
+QZ_METADATA_OVERFLOW, QZ_OUT_OF_RANGE = -118, -119
 QZ_DEFLATE_4B, QZ_DEFLATE_GZIP, QZ_DEFLATE_GZIP_EXT, QZ_DEFLATE_RAW = 0, 1, 2, 3
 QZ_DEFLATE, QZ_LZ4 = 8, ord("4")
 QZ_DIR_COMPRESS, QZ_DIR_DECOMPRESS, QZ_DIR_BOTH = 0, 1, 2
@@ -57,6 +58,16 @@ class QzResult(C.Structure):
                 ("ext_rc", C.c_uint64), ("crc", C.c_void_p), ("extension_result", C.c_void_p)]
 
 
+class QzCrc64Config(C.Structure):
+    _fields_ = [("polynomial", C.c_uint64), ("initial_value", C.c_uint64), ("reflect_in", C.c_uint32),
+                ("reflect_out", C.c_uint32), ("xor_out", C.c_uint64)]
+
+
+class QzCrc32Config(C.Structure):
+    _fields_ = [("polynomial", C.c_uint32), ("initial_value", C.c_uint32), ("reflect_in", C.c_uint32),
+                ("reflect_out", C.c_uint32), ("xor_out", C.c_uint32)]
+
+
 QzAsyncCallback = C.CFUNCTYPE(C.c_int, C.POINTER(QzResult))
 
 _bound = False
@@ -94,8 +105,61 @@ def lib():
         L.qzSetLogLevel.argtypes = [C.c_int]
         L.qzCompress2.argtypes = [P(QzSession), C.c_void_p, C.c_void_p, C.c_void_p, P(QzResult)]
         L.qzDecompress2.argtypes = [P(QzSession), C.c_void_p, C.c_void_p, C.c_void_p, P(QzResult)]
+        u32p, u64p = P(C.c_uint32), P(C.c_uint64)
+        L.qzCompressCrc64.argtypes = [P(QzSession), u8p, up, C.c_void_p, up, C.c_uint, u64p]
+        L.qzCompressCrc64Ext.argtypes = [P(QzSession), u8p, up, C.c_void_p, up, C.c_uint, u64p, u64p]
+        L.qzDecompressCrc64.argtypes = [P(QzSession), u8p, up, C.c_void_p, up, u64p]
+        L.qzDecompressCrc64Ext.argtypes = [P(QzSession), u8p, up, C.c_void_p, up, u64p, u64p]
+        L.qzCompressWithMetadataExt.argtypes = [P(QzSession), u8p, up, C.c_void_p, up, C.c_uint, u64p, C.c_void_p, C.c_uint32, C.c_uint32]
+        L.qzDecompressWithMetadataExt.argtypes = [P(QzSession), u8p, up, C.c_void_p, up, u64p, C.c_void_p, C.c_uint32]
+        L.qzAllocateMetadata.argtypes = [P(C.c_void_p), C.c_size_t, C.c_uint32]
+        L.qzFreeMetadata.argtypes = [C.c_void_p]
+        L.qzMetadataBlockRead.argtypes = [C.c_uint32, C.c_void_p, u32p, u32p, u32p, u32p]
+        L.qzMetadataBlockWrite.argtypes = [C.c_uint32, C.c_void_p, u32p, u32p, u32p, u32p]
+        L.qzMetadataBlockGetCrc64.argtypes = [C.c_uint32, C.c_void_p, u64p, u64p]
+        L.qzMetadataBlockGetCrc32.argtypes = [C.c_uint32, C.c_void_p, u32p, u32p]
+        L.qzGetSessionCrc64Config.argtypes = [P(QzSession), P(QzCrc64Config)]
+        L.qzSetSessionCrc64Config.argtypes = [P(QzSession), P(QzCrc64Config)]
+        L.qzGetSessionCrc32Config.argtypes = [P(QzSession), P(QzCrc32Config)]
+        L.qzSetSessionCrc32Config.argtypes = [P(QzSession), P(QzCrc32Config)]
         _bound = True
     return L
+
+
+class Metadata:
+    """A QzMetadataBlob_T (qzAllocateMetadata): one record per hw_buff_sz block of data_size bytes."""
+
+    def __init__(self, data_size, hw_buff_sz):
+        self.L = lib()
+        self.h = C.c_void_p()
+        self.rc_alloc = self.L.qzAllocateMetadata(C.byref(self.h), data_size, hw_buff_sz)
+
+    def read(self, k):
+        """-> (rc, offset, size, flags, hash)"""
+        o, z, f, h = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+        rc = self.L.qzMetadataBlockRead(k, self.h, C.byref(o), C.byref(z), C.byref(f), C.byref(h))
+        return rc, o.value, z.value, f.value, h.value
+
+    def write(self, k, offset=None, size=None, flags=None, hash=None):
+        """qzMetadataBlockWrite; a field left None is passed as NULL (not written)"""
+        a = [None if v is None else C.byref(C.c_uint32(v)) for v in (offset, size, flags, hash)]
+        return self.L.qzMetadataBlockWrite(k, self.h, *a)
+
+    def crc32(self, k):
+        """-> (rc, input_crc, output_crc)"""
+        i, o = C.c_uint32(), C.c_uint32()
+        rc = self.L.qzMetadataBlockGetCrc32(k, self.h, C.byref(i), C.byref(o))
+        return rc, i.value, o.value
+
+    def crc64(self, k):
+        i, o = C.c_uint64(), C.c_uint64()
+        rc = self.L.qzMetadataBlockGetCrc64(k, self.h, C.byref(i), C.byref(o))
+        return rc, i.value, o.value
+
+    def free(self):
+        rc = self.L.qzFreeMetadata(self.h) if self.h else QZ_PARAMS
+        self.h = C.c_void_p()
+        return rc
 
 
 class Session:
@@ -148,6 +212,59 @@ class Session:
             rc = self.L.qzDecompressCrc(C.byref(self.s), comp, C.byref(sl), dst, C.byref(dl), C.byref(crc))
             return rc, sl.value, dst.raw[:dl.value], crc.value
         rc = self.L.qzDecompress(C.byref(self.s), comp, C.byref(sl), dst, C.byref(dl))
+        return rc, sl.value, dst.raw[:dl.value]
+
+    def compress_crc64(self, src: bytes, crc0=0, last=1, cap=None):
+        """qzCompressCrc64 -> (rc, consumed, out_bytes, crc): crc0 = the finalised CRC-64 of the bytes before this call"""
+        if cap is None:
+            cap = self.L.qzMaxCompressedLength(max(len(src), 1), C.byref(self.s)) + 64
+        sl, dl, crc = C.c_uint(len(src)), C.c_uint(cap), C.c_uint64(crc0)
+        dst = C.create_string_buffer(max(cap, 1))
+        rc = self.L.qzCompressCrc64(C.byref(self.s), src, C.byref(sl), dst, C.byref(dl), last, C.byref(crc))
+        return rc, sl.value, dst.raw[:dl.value], crc.value
+
+    def decompress_crc64(self, comp: bytes, cap: int, crc0=0):
+        """qzDecompressCrc64 -> (rc, consumed, out_bytes, crc of the output)"""
+        sl, dl, crc = C.c_uint(len(comp)), C.c_uint(cap), C.c_uint64(crc0)
+        dst = C.create_string_buffer(max(cap, 1))
+        rc = self.L.qzDecompressCrc64(C.byref(self.s), comp, C.byref(sl), dst, C.byref(dl), C.byref(crc))
+        return rc, sl.value, dst.raw[:dl.value], crc.value
+
+    def set_crc64(self, polynomial, initial_value, reflect_in, reflect_out, xor_out):
+        g = QzCrc64Config(polynomial, initial_value, reflect_in, reflect_out, xor_out)
+        return self.L.qzSetSessionCrc64Config(C.byref(self.s), C.byref(g))
+
+    def set_crc32(self, polynomial, initial_value, reflect_in, reflect_out, xor_out):
+        g = QzCrc32Config(polynomial, initial_value, reflect_in, reflect_out, xor_out)
+        return self.L.qzSetSessionCrc32Config(C.byref(self.s), C.byref(g))
+
+    def get_crc64(self):
+        g = QzCrc64Config()
+        rc = self.L.qzGetSessionCrc64Config(C.byref(self.s), C.byref(g))
+        return rc, (g.polynomial, g.initial_value, g.reflect_in, g.reflect_out, g.xor_out)
+
+    def get_crc32(self):
+        g = QzCrc32Config()
+        rc = self.L.qzGetSessionCrc32Config(C.byref(self.s), C.byref(g))
+        return rc, (g.polynomial, g.initial_value, g.reflect_in, g.reflect_out, g.xor_out)
+
+    def compress_meta(self, src: bytes, meta, thrshold, override=0, cap=None, last=1):
+        """qzCompressWithMetadataExt -> (rc, consumed, out_bytes); last_ext_rc <- what the call left in *ext_rc"""
+        if cap is None:
+            cap = len(src) + len(src) // 8 + 1024
+        sl, dl = C.c_uint(len(src)), C.c_uint(cap)
+        dst = C.create_string_buffer(max(cap, 1))
+        ext = C.c_uint64(7)
+        rc = self.L.qzCompressWithMetadataExt(C.byref(self.s), src, C.byref(sl), dst, C.byref(dl), last, C.byref(ext), meta.h,
+                                              override, thrshold)
+        self.last_ext_rc = ext.value
+        return rc, sl.value, dst.raw[:dl.value]
+
+    def decompress_meta(self, comp: bytes, meta, cap, override=0):
+        """qzDecompressWithMetadataExt -> (rc, consumed, out_bytes)"""
+        sl, dl = C.c_uint(len(comp)), C.c_uint(cap)
+        dst = C.create_string_buffer(max(cap, 1))
+        rc = self.L.qzDecompressWithMetadataExt(C.byref(self.s), comp, C.byref(sl), dst, C.byref(dl), None, meta.h, override)
         return rc, sl.value, dst.raw[:dl.value]
 
     def end_of_stream(self):

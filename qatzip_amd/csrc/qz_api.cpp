@@ -57,6 +57,9 @@ struct Sess {
      * chunk), true = the hardware path's (one complete member per hw_buff_sz chunk, src/qatzip.c:1691-1718) */
     bool hw_framing;
     std::vector<unsigned char> hw_stage;
+    /* the CRCs of the Crc64 calls and of the metadata records (qzSetSessionCrc64Config / Crc32Config); nothing else reads them */
+    QzCrc64Config_T crc64; QzCrc32Config_T crc32;
+    bool out_resident;              /* the last decompress call left its output at d_out (not handed out of d_hold) */
 };
 
 static pthread_mutex_t g_lock = PTHREAD_MUTEX_INITIALIZER, g_mem_lock = PTHREAD_MUTEX_INITIALIZER;
@@ -68,6 +71,9 @@ static const Params k_factory = {QZ_HUFF_HDR_DEFAULT, QZ_DIRECTION_DEFAULT, F_GZ
                                  QZ_STRM_BUFF_SZ_DEFAULT, QZ_COMP_THRESHOLD_DEFAULT, QZ_REQ_THRESHOLD_DEFAULT,
                                  QZ_WAIT_CNT_THRESHOLD_DEFAULT, QZ_PERIODICAL_POLLING, 0, 0, 0, NULL, NULL, 3};
 static Params g_def = k_factory;
+/* CRC-64/ECMA-182 as include/qatzip.h documents the default; the gzip CRC-32 in the same model (= zlib's crc32()) */
+static const QzCrc64Config_T k_crc64_default = {0x42F0E1EBA9EA3693ull, 0, 0, 0, 0};
+static const QzCrc32Config_T k_crc32_default = {0x04C11DB7u, 0xFFFFFFFFu, 1, 1, 0xFFFFFFFFu};
 
 static void logmsg(QzLogLevel_T lvl, const char *fmt, ...)
 {
@@ -244,6 +250,7 @@ static int make_session(QzSession_T *sess, const Params &p)
     s->p = p; s->ctx = NULL; s->d_in = s->d_out = NULL; s->in_cap = s->out_cap = 0;
     s->d_hold = NULL; s->hold_len = s->hold_pos = 0;
     s->open = false; s->run_sum = 0; s->st_in = s->st_out = 0; s->end_of_stream = 0;
+    s->crc64 = k_crc64_default; s->crc32 = k_crc32_default; s->out_resident = false;
     {
         const char *e = getenv("QATZIP_AMD_HW_FRAMING");
         s->hw_framing = e && e[0] == '1';
@@ -652,6 +659,7 @@ static int decompress_lz4(QzSession_T *sess, Sess *s, const unsigned char *src, 
 {
     const uint32_t n = *src_len, cap = *dest_len;
     *src_len = 0; *dest_len = 0;
+    s->out_resident = false;
     std::vector<qzd_lz4seg> segs;
     uint32_t ti = 0; uint64_t to = 0;
     while (ti < n && to < cap) {                                    /* frame loop, src/qatzip_sw.c:555-571 */
@@ -681,6 +689,7 @@ static int decompress_lz4(QzSession_T *sess, Sess *s, const unsigned char *src, 
         produced = segs[i].out_off + res[i].out_len;
     }
     if (produced && qzd_d2h(s->ctx, dest, s->d_out, produced) != QZD_OK) return QZ_FAIL;
+    s->out_resident = true;
     *src_len = ti; *dest_len = (unsigned int)produced;
     sess->total_in += ti; sess->total_out += produced;
     return (ti < n && to >= cap) ? QZ_OK : QZ_OK;
@@ -827,6 +836,7 @@ static int decompress_deflate(QzSession_T *sess, Sess *s, const unsigned char *s
 {
     const int fmt = s->p.fmt;
     const uint32_t n = *src_len, cap = *dest_len;
+    s->out_resident = false;
     if (s->d_hold) {
         /* the rest of a member that was larger than the destination (below): the next piece; the member's last input
          * byte was held back for exactly this, and goes with the last piece */
@@ -943,6 +953,7 @@ static int decompress_deflate(QzSession_T *sess, Sess *s, const unsigned char *s
     if (to && !(all_sent && sent_bytes == to) && qzd_d2h(s->ctx, dest, s->d_out, to) != QZD_OK) return QZ_FAIL;
     *src_len = ti; *dest_len = to;
     sess->total_in += ti; sess->total_out += to;
+    s->out_resident = true;
     return ret;
 }
 
@@ -1550,24 +1561,309 @@ extern "C" int qzCompress2(QzSession_T *sess, const unsigned char *src, unsigned
 extern "C" int qzDecompress2(QzSession_T *sess, const unsigned char *src, unsigned char *dest, qzAsyncCallbackFn callback, QzResult_T *qzResults)
 { return submit2(sess, src, dest, callback, qzResults, false); }
 
-/* ------------------------------------------------------------------ declared-only surface */
-#define NS(...) { return QZ_NOT_SUPPORTED; }
-extern "C" int qzCompressCrc64(QzSession_T *, const unsigned char *, unsigned int *, unsigned char *, unsigned int *, unsigned int, uint64_t *) NS()
-extern "C" int qzCompressCrc64Ext(QzSession_T *, const unsigned char *, unsigned int *, unsigned char *, unsigned int *, unsigned int, uint64_t *, uint64_t *) NS()
-extern "C" int qzDecompressCrc64(QzSession_T *, const unsigned char *, unsigned int *, unsigned char *, unsigned int *, uint64_t *) NS()
-extern "C" int qzDecompressCrc64Ext(QzSession_T *, const unsigned char *, unsigned int *, unsigned char *, unsigned int *, uint64_t *, uint64_t *) NS()
-extern "C" int qzCompressWithMetadataExt(QzSession_T *, const unsigned char *, unsigned int *, unsigned char *, unsigned int *, unsigned int, uint64_t *, QzMetadataBlob_T, uint32_t, uint32_t) NS()
-extern "C" int qzDecompressWithMetadataExt(QzSession_T *, const unsigned char *, unsigned int *, unsigned char *, unsigned int *, uint64_t *, QzMetadataBlob_T, uint32_t) NS()
-extern "C" int qzAllocateMetadata(QzMetadataBlob_T *, size_t, uint32_t) NS()
-extern "C" int qzFreeMetadata(QzMetadataBlob_T) NS()
-extern "C" int qzMetadataBlockRead(uint32_t, QzMetadataBlob_T, uint32_t *, uint32_t *, uint32_t *, uint32_t *) NS()
-extern "C" int qzMetadataBlockWrite(uint32_t, QzMetadataBlob_T, uint32_t *, uint32_t *, uint32_t *, uint32_t *) NS()
-extern "C" int qzMetadataBlockGetCrc64(uint32_t, QzMetadataBlob_T, uint64_t *, uint64_t *) NS()
-extern "C" int qzMetadataBlockGetCrc32(uint32_t, QzMetadataBlob_T, uint32_t *, uint32_t *) NS()
-extern "C" int qzGetSessionCrc64Config(QzSession_T *, QzCrc64Config_T *) NS()
-extern "C" int qzGetSessionCrc32Config(QzSession_T *, QzCrc32Config_T *) NS()
-extern "C" int qzSetSessionCrc64Config(QzSession_T *, QzCrc64Config_T *) NS()
-extern "C" int qzSetSessionCrc32Config(QzSession_T *, QzCrc32Config_T *) NS()
+/* ------------------------------------------------------------------ CRC configs, the Crc64 calls
+ * The reference declares and documents these (include/qatzip.h:1326-1341, :1652-1666, :2722-2862) and defines none of them
+ * (SURVEY.md fact 10); its header is the specification, INTEGRATION.md holds what it leaves open.  A config governs the
+ * Crc64 calls and the CRCs of the metadata records only: the wire formats' trailers and qzCompressCrc's crc stay zlib's. */
+static Sess *setup_sess(QzSession_T *sess) { return sess ? (Sess *)sess->internal : NULL; }
+template <typename T> static bool crc_cfg_ok(const T *g) { return g->reflect_in <= 1 && g->reflect_out <= 1 && (g->polynomial & 1); }
+
+extern "C" int qzGetSessionCrc64Config(QzSession_T *sess, QzCrc64Config_T *g)
+{
+    if (!sess || !g) return QZ_PARAMS;
+    Sess *s = setup_sess(sess);
+    if (!s) return QZ_FAIL;
+    *g = s->crc64;
+    return QZ_OK;
+}
+extern "C" int qzGetSessionCrc32Config(QzSession_T *sess, QzCrc32Config_T *g)
+{
+    if (!sess || !g) return QZ_PARAMS;
+    Sess *s = setup_sess(sess);
+    if (!s) return QZ_FAIL;
+    *g = s->crc32;
+    return QZ_OK;
+}
+extern "C" int qzSetSessionCrc64Config(QzSession_T *sess, QzCrc64Config_T *g)
+{
+    if (!sess || !g) return QZ_PARAMS;
+    Sess *s = setup_sess(sess);
+    if (!s) return QZ_FAIL;
+    if (!crc_cfg_ok(g)) return QZ_PARAMS;
+    s->crc64 = *g;
+    return QZ_OK;
+}
+extern "C" int qzSetSessionCrc32Config(QzSession_T *sess, QzCrc32Config_T *g)
+{
+    if (!sess || !g) return QZ_PARAMS;
+    Sess *s = setup_sess(sess);
+    if (!s) return QZ_FAIL;
+    if (!crc_cfg_ok(g)) return QZ_PARAMS;
+    s->crc32 = *g;
+    return QZ_OK;
+}
+static qzd_crccfg dev_cfg(const QzCrc64Config_T &g) { qzd_crccfg c = {g.polynomial, g.initial_value, g.reflect_in, g.reflect_out, g.xor_out}; return c; }
+static qzd_crccfg dev_cfg(const QzCrc32Config_T &g) { qzd_crccfg c = {g.polynomial, g.initial_value, g.reflect_in, g.reflect_out, g.xor_out}; return c; }
+
+/* *crc, the finalised CRC-64 of the bytes before, taken over the len bytes at d_data (zlib's crc32() chaining) */
+static int crc64_chain(Sess *s, const uint8_t *d_data, uint32_t len, uint64_t *crc)
+{
+    const qzd_range rg = {0, len, 0};
+    const qzd_crccfg cfg = dev_cfg(s->crc64);
+    uint64_t out = 0;
+    if (qzd_crcn_ranges(s->ctx, d_data, &rg, 1, 64, &cfg, crc, &out) != QZD_OK) return QZ_FAIL;
+    *crc = out;
+    return QZ_OK;
+}
+
+/* qzCompressCrc[Ext] on the direct path (never the shared queue: the input has to be this session's device copy), with
+ * *crc the CRC-64 of the input consumed */
+extern "C" int qzCompressCrc64Ext(QzSession_T *sess, const unsigned char *src, unsigned int *src_len, unsigned char *dest,
+                                  unsigned int *dest_len, unsigned int last, uint64_t *crc, uint64_t *ext_rc)
+{
+    int rc = compress_direct(sess, src, src_len, dest, dest_len, last, NULL, ext_rc, false);
+    if ((rc == QZ_OK || rc == QZ_BUF_ERROR) && crc && *src_len) {
+        Sess *s = (Sess *)sess->internal;                           /* the consumed bytes stand at d_in: every compress path stages them there */
+        if (crc64_chain(s, s->d_in, *src_len, crc) != QZ_OK) { *src_len = 0; *dest_len = 0; return QZ_FAIL; }
+    }
+    return rc;
+}
+extern "C" int qzCompressCrc64(QzSession_T *sess, const unsigned char *src, unsigned int *src_len, unsigned char *dest,
+                               unsigned int *dest_len, unsigned int last, uint64_t *crc)
+{ return qzCompressCrc64Ext(sess, src, src_len, dest, dest_len, last, crc, NULL); }
+
+/* qzDecompress[Ext] on the direct path, with *crc the CRC-64 of the output produced */
+extern "C" int qzDecompressCrc64Ext(QzSession_T *sess, const unsigned char *src, unsigned int *src_len, unsigned char *dest,
+                                    unsigned int *dest_len, uint64_t *crc, uint64_t *ext_rc)
+{
+    int rc = decompress_direct(sess, src, src_len, dest, dest_len, NULL, ext_rc, false);
+    if ((rc == QZ_OK || rc == QZ_BUF_ERROR) && crc && *dest_len) {
+        Sess *s = (Sess *)sess->internal;
+        /* a member handed out piece by piece (decompress_deflate, d_hold) is not at d_out: the piece goes back there */
+        if (!s->out_resident && (reserve(s, 0, *dest_len) != QZ_OK || qzd_h2d(s->ctx, s->d_out, dest, *dest_len) != QZD_OK)) rc = QZ_FAIL;
+        else if (crc64_chain(s, s->d_out, *dest_len, crc) != QZ_OK) rc = QZ_FAIL;
+        if (rc == QZ_FAIL) { *src_len = 0; *dest_len = 0; }
+    }
+    return rc;
+}
+extern "C" int qzDecompressCrc64(QzSession_T *sess, const unsigned char *src, unsigned int *src_len, unsigned char *dest,
+                                 unsigned int *dest_len, uint64_t *crc)
+{ return qzDecompressCrc64Ext(sess, src, src_len, dest, dest_len, crc, NULL); }
+
+/* ------------------------------------------------------------------ metadata blobs (include/qatzip.h:2184-2307, :2864-3101)
+ * Host memory, no device involved: a header and one record per hw_buff_sz block of data_size.  Every record carries a check
+ * word over its fields; qzMetadataBlockWrite refreshes it, the CRC getters refuse a record whose word does not match. */
+#define QZ_META_MAGIC 0x444D5A51u                                   /* "QZMD" */
+#define QZ_META_MAX_DATA (1ull << 30)
+struct MetaHdr { uint32_t magic, nblocks, hw_buff_sz, pad; uint64_t data_size, pad2; };
+struct MetaRec { uint32_t offset, size, flags, hash, in_crc32, out_crc32, check, pad; uint64_t in_crc64, out_crc64; };
+
+static uint32_t meta_check(const MetaRec &r)
+{
+    const uint32_t w[10] = {r.offset, r.size, r.flags, r.hash, r.in_crc32, r.out_crc32, (uint32_t)r.in_crc64,
+                            (uint32_t)(r.in_crc64 >> 32), (uint32_t)r.out_crc64, (uint32_t)(r.out_crc64 >> 32)};
+    uint32_t h = 0x811C9DC5u;                                       /* FNV-1a over the words */
+    for (int i = 0; i < 10; i++) { h ^= w[i]; h *= 16777619u; h ^= h >> 15; }
+    return h;
+}
+static bool hw_buff_ok(uint32_t b) { return b >= QZ_HW_BUFF_MIN_SZ && b <= QZ_HW_BUFF_MAX_SZ && !(b & (b - 1)); }
+static MetaHdr *meta_hdr(QzMetadataBlob_T m) { MetaHdr *h = (MetaHdr *)m; return h && h->magic == QZ_META_MAGIC ? h : NULL; }
+static MetaRec *meta_recs(MetaHdr *h) { return (MetaRec *)(h + 1); }
+
+extern "C" int qzAllocateMetadata(QzMetadataBlob_T *metadata, size_t data_size, uint32_t hw_buff_sz)
+{
+    if (!metadata || data_size == 0 || data_size > QZ_META_MAX_DATA || !hw_buff_ok(hw_buff_sz)) return QZ_PARAMS;
+    const uint32_t nb = (uint32_t)((data_size + hw_buff_sz - 1) / hw_buff_sz);
+    MetaHdr *h = (MetaHdr *)calloc(1, sizeof(MetaHdr) + (size_t)nb * sizeof(MetaRec));
+    if (!h) return QZ_FAIL;
+    h->magic = QZ_META_MAGIC; h->nblocks = nb; h->hw_buff_sz = hw_buff_sz; h->data_size = data_size;
+    MetaRec *r = meta_recs(h);
+    for (uint32_t k = 0; k < nb; k++) r[k].check = meta_check(r[k]);
+    *metadata = h;
+    return QZ_OK;
+}
+extern "C" int qzFreeMetadata(QzMetadataBlob_T metadata)
+{
+    MetaHdr *h = meta_hdr(metadata);
+    if (!h) return QZ_PARAMS;
+    h->magic = 0;
+    free(h);
+    return QZ_OK;
+}
+extern "C" int qzMetadataBlockRead(uint32_t block_num, QzMetadataBlob_T metadata, uint32_t *block_offset, uint32_t *block_size,
+                                   uint32_t *block_flags, uint32_t *block_hash)
+{
+    MetaHdr *h = meta_hdr(metadata);
+    if (!h) return QZ_PARAMS;
+    if (block_num >= h->nblocks) return QZ_OUT_OF_RANGE;
+    const MetaRec &r = meta_recs(h)[block_num];
+    if (block_offset) *block_offset = r.offset;
+    if (block_size) *block_size = r.size;
+    if (block_flags) *block_flags = r.flags;
+    if (block_hash) *block_hash = r.hash;
+    return QZ_OK;
+}
+extern "C" int qzMetadataBlockWrite(uint32_t block_num, QzMetadataBlob_T metadata, uint32_t *block_offset, uint32_t *block_size,
+                                    uint32_t *block_flags, uint32_t *block_hash)
+{
+    MetaHdr *h = meta_hdr(metadata);
+    if (!h) return QZ_PARAMS;
+    if (block_num >= h->nblocks) return QZ_OUT_OF_RANGE;
+    MetaRec &r = meta_recs(h)[block_num];
+    if (block_offset) r.offset = *block_offset;
+    if (block_size) r.size = *block_size;
+    if (block_flags) r.flags = *block_flags;
+    if (block_hash) r.hash = *block_hash;
+    r.check = meta_check(r);
+    return QZ_OK;
+}
+extern "C" int qzMetadataBlockGetCrc64(uint32_t block_num, QzMetadataBlob_T metadata, uint64_t *input_crc, uint64_t *output_crc)
+{
+    MetaHdr *h = meta_hdr(metadata);
+    if (!h) return QZ_PARAMS;
+    if (block_num >= h->nblocks) return QZ_OUT_OF_RANGE;
+    const MetaRec &r = meta_recs(h)[block_num];
+    if (r.check != meta_check(r)) return QZ_PARAMS;
+    if (input_crc) *input_crc = r.in_crc64;
+    if (output_crc) *output_crc = r.out_crc64;
+    return QZ_OK;
+}
+extern "C" int qzMetadataBlockGetCrc32(uint32_t block_num, QzMetadataBlob_T metadata, uint32_t *input_crc, uint32_t *output_crc)
+{
+    MetaHdr *h = meta_hdr(metadata);
+    if (!h) return QZ_PARAMS;
+    if (block_num >= h->nblocks) return QZ_OUT_OF_RANGE;
+    const MetaRec &r = meta_recs(h)[block_num];
+    if (r.check != meta_check(r)) return QZ_PARAMS;
+    if (input_crc) *input_crc = r.in_crc32;
+    if (output_crc) *output_crc = r.out_crc32;
+    return QZ_OK;
+}
+
+/* ------------------------------------------------------------------ compress / decompress with metadata
+ * include/qatzip.h:1343-1455, :1668-1754.  QZ_DEFLATE_RAW sessions only.  The call's input is cut every B bytes
+ * (hw_buff_sz_override, or the session's hw_buff_sz); block k is the raw-deflate stream of its bytes alone, closed with
+ * BFINAL - or, when that stream is longer than comp_thrshold, the bytes themselves - and the blocks stand back to back in
+ * the destination.  The blob gets offset, size, flag, XXH32 of the plaintext and the four CRCs of every block; all of it is
+ * computed on the device (qzd_blocks_compress), nothing goes through the shared queue. */
+static int meta_block_sz(const Sess *s, uint32_t override, uint32_t *B)
+{
+    if (override && !hw_buff_ok(override)) return QZ_PARAMS;
+    *B = override ? override : s->p.hw_buff_sz;
+    return QZ_OK;
+}
+
+extern "C" int qzCompressWithMetadataExt(QzSession_T *sess, const unsigned char *src, unsigned int *src_len, unsigned char *dest,
+                                         unsigned int *dest_len, unsigned int last, uint64_t *ext_rc, QzMetadataBlob_T metadata,
+                                         uint32_t hw_buff_sz_override, uint32_t comp_thrshold)
+{
+    int rc; Sess *s = NULL; uint32_t B = 0;
+    MetaHdr *h = meta_hdr(metadata);
+    if (!sess || !src || !src_len || !dest || !dest_len || (last != 0 && last != 1) || !h) { rc = QZ_PARAMS; goto fail; }
+    if (ext_rc) *ext_rc = 0;
+    rc = ensure_ready(sess, &s);
+    if (rc < 0) goto fail;
+    if (s->p.fmt != F_RAW || s->p.comp_lvl < 1 || s->p.comp_lvl > 9) { rc = QZ_NOT_SUPPORTED; goto fail; }
+    rc = meta_block_sz(s, hw_buff_sz_override, &B);
+    if (rc) goto fail;
+    {
+        const uint32_t n = *src_len, cap = *dest_len;
+        if (n == 0) { *dest_len = 0; return QZ_OK; }
+        const uint32_t nb = (uint32_t)(((uint64_t)n + B - 1) / B);
+        if (nb > h->nblocks) { rc = QZ_METADATA_OVERFLOW; goto fail; }
+        const uint64_t worst = (uint64_t)n + (uint64_t)nb * (5ull * (B / 32767 + 2) + 16) + 64;
+        rc = reserve(s, (uint64_t)nb * B, worst);
+        if (rc) goto fail;
+        if (qzd_h2d(s->ctx, s->d_in, src, n) != QZD_OK) { rc = QZ_FAIL; goto fail; }
+        std::vector<qzd_blockrec> recs(nb);
+        const qzd_crccfg c32 = dev_cfg(s->crc32), c64 = dev_cfg(s->crc64);
+        uint64_t produced = 0;
+        /* the device's destination holds every block; which of them the caller's holds is decided here */
+        if (qzd_blocks_compress(s->ctx, s->d_in, n, B, (int)s->p.comp_lvl, comp_thrshold, &c32, &c64, s->d_out, s->out_cap,
+                                recs.data(), &produced) != QZD_OK) {
+            logmsg(LOG_ERROR, "GPU block compress failed: %s\n", qzd_last_error(s->ctx));
+            rc = QZ_FAIL; goto fail;
+        }
+        uint32_t take = 0; uint64_t bytes = 0;
+        while (take < nb && recs[take].offset + recs[take].size <= cap) { bytes = recs[take].offset + recs[take].size; take++; }
+        if (take == 0) { rc = QZ_BUF_ERROR; goto fail; }
+        if (bytes && qzd_d2h(s->ctx, dest, s->d_out, bytes) != QZD_OK) { rc = QZ_FAIL; goto fail; }
+        MetaRec *mr = meta_recs(h);
+        for (uint32_t k = 0; k < take; k++) {
+            MetaRec &r = mr[k]; const qzd_blockrec &d = recs[k];
+            r.offset = (uint32_t)d.offset; r.size = d.size; r.flags = d.flags; r.hash = d.hash;
+            r.in_crc32 = d.in_crc32; r.out_crc32 = d.out_crc32; r.in_crc64 = d.in_crc64; r.out_crc64 = d.out_crc64;
+            r.check = meta_check(r);
+        }
+        const uint32_t used = take == nb ? n : take * B;
+        *src_len = used; *dest_len = (unsigned int)bytes;
+        sess->total_in += used; sess->total_out += bytes;
+        rc = take == nb ? QZ_OK : QZ_BUF_ERROR;
+        sess->thd_sess_stat = rc;
+        return rc;
+    }
+fail:
+    if (src_len) *src_len = 0;
+    if (dest_len) *dest_len = 0;
+    return rc;
+}
+
+/* The blocks are the leading records with a size; block k is read at src + its offset and its plaintext written to
+ * dest + k * B, so a blob of one record (qzMetadataBlockWrite) decodes that block alone.  The blob is not modified. */
+extern "C" int qzDecompressWithMetadataExt(QzSession_T *sess, const unsigned char *src, unsigned int *src_len, unsigned char *dest,
+                                           unsigned int *dest_len, uint64_t *ext_rc, QzMetadataBlob_T metadata,
+                                           uint32_t hw_buff_sz_override)
+{
+    int rc; Sess *s = NULL; uint32_t B = 0;
+    MetaHdr *h = meta_hdr(metadata);
+    if (!sess || !src || !src_len || !dest || !dest_len || !h) { rc = QZ_PARAMS; goto fail; }
+    if (ext_rc) *ext_rc = 0;
+    rc = ensure_ready(sess, &s);
+    if (rc < 0) goto fail;
+    if (s->p.fmt != F_RAW) { rc = QZ_NOT_SUPPORTED; goto fail; }
+    rc = meta_block_sz(s, hw_buff_sz_override, &B);
+    if (rc) goto fail;
+    {
+        const uint32_t n = *src_len, cap = *dest_len;
+        const MetaRec *mr = meta_recs(h);
+        uint32_t nb = 0;
+        while (nb < h->nblocks && mr[nb].size) nb++;
+        if (n == 0 || nb == 0) { *src_len = 0; *dest_len = 0; return QZ_OK; }
+        std::vector<qzd_blockrec> recs(nb);
+        uint64_t end = 0;
+        for (uint32_t k = 0; k < nb; k++) {
+            qzd_blockrec &d = recs[k];
+            memset(&d, 0, sizeof(d));
+            d.offset = mr[k].offset; d.size = mr[k].size; d.flags = mr[k].flags ? 1 : 0; d.hash = mr[k].hash;
+            if (d.offset + d.size > n) { rc = QZ_DATA_ERROR; goto fail; }
+            end = std::max<uint64_t>(end, d.offset + d.size);
+        }
+        if ((uint64_t)(nb - 1) * B >= cap) { rc = QZ_BUF_ERROR; goto fail; }
+        rc = reserve(s, end, (uint64_t)nb * B);
+        if (rc) goto fail;
+        if (qzd_h2d(s->ctx, s->d_in, src, end) != QZD_OK) { rc = QZ_FAIL; goto fail; }
+        uint64_t produced = 0;
+        const int r = qzd_blocks_decompress(s->ctx, s->d_in, end, recs.data(), nb, B, s->d_out, (uint64_t)nb * B, NULL, &produced);
+        if (r == QZD_ERR_DATA) { rc = QZ_DATA_ERROR; goto fail; }
+        if (r == QZD_ERR_DSTCAP) { rc = QZ_BUF_ERROR; goto fail; }
+        if (r == QZD_ERR_NOMEM) { rc = QZ_NOSW_LOW_MEM; goto fail; }
+        if (r != QZD_OK) { logmsg(LOG_ERROR, "GPU block decompress failed: %s\n", qzd_last_error(s->ctx)); rc = QZ_FAIL; goto fail; }
+        if (produced > cap) { rc = QZ_BUF_ERROR; goto fail; }
+        if (produced && qzd_d2h(s->ctx, dest, s->d_out, produced) != QZD_OK) { rc = QZ_FAIL; goto fail; }
+        *src_len = (unsigned int)end; *dest_len = (unsigned int)produced;
+        sess->total_in += end; sess->total_out += produced;
+        sess->thd_sess_stat = QZ_OK;
+        return QZ_OK;
+    }
+fail:
+    if (src_len) *src_len = 0;
+    if (dest_len) *dest_len = 0;
+    return rc;
+}
+
+/* ------------------------------------------------------------------ declared-only surface
+ * what is left of it: LZ4s (qzSetupSessionLZ4S / qzSetDefaultsLZ4S above, QAT-2.0 silicon only) answers QZ_NOT_SUPPORTED;
+ * the two version queries below answer for this library */
 extern "C" int qzGetSoftwareComponentCount(unsigned int *n) { if (!n) return QZ_PARAMS; *n = 1; return QZ_OK; }
 extern "C" int qzGetSoftwareComponentVersionList(QzSoftwareVersionInfo_T *info, unsigned int *n)
 {

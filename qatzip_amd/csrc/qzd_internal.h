@@ -60,6 +60,7 @@ struct qzd_ctx {
     uint8_t *d_big; size_t big_cap; uint32_t big_small;   /* device-only scratch (per-segment decode tables of K3b); calls in a row that needed under a quarter of it */
     uint32_t *d_cdesc; size_t cdesc_cap;            /* per-slot descriptors of a coalesced launch (qzd_deflate_slots); capacity in bytes */
     uint8_t *d_lane; size_t lane_cap;               /* device-only scratch of the lane, wide, lazy and LZ4-HC compress paths (carve_symbols) */
+    uint8_t *d_meta; size_t meta_cap;               /* device-only scratch of the block calls (qzd_meta.hip): slot streams, plan, ranges, hashes, CRCs */
     float inf_ms[4];
     int lz4d_route;                 /* qzd_lz4_decode_route: 0 auto, 1 a wave per frame, 2 a wave per block wherever a frame qualifies */
     bool no_stream_in;              /* this call is the batched retry of a launch that gave up waiting for its input */
