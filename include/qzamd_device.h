@@ -256,6 +256,17 @@ int qzd_lz4hc_compress_frames_hw(qzd_ctx *ctx, const uint8_t *d_src, uint64_t n,
                                  uint64_t dst_cap, uint64_t *h_out_len, uint32_t *h_frame_len);
 int qzd_lz4hc_compress_linked(qzd_ctx *ctx, const uint8_t *d_src, uint64_t n, int level, uint8_t *d_dst, uint64_t dst_cap,
                               uint64_t *h_out_len);
+/* LZ4s (the LZ77 sequence blocks a QAT device hands to a session's post-processing callback; the format is in
+ * INTEGRATION.md, "LZ4s sessions"): every block_sz bytes of d_src become one block - u32le size, then the sequences - back
+ * to back in d_dst, the last one of what is left.  No header, no end mark, no checksum.  One wave per block (K4s,
+ * qzk_lz4s.h), one launch plus scan and gather per round of blocks.
+ * qzd_lz4s_bound: what the blocks of n bytes can grow to - per block of c bytes 4 + c + c/255 + 4*ceil(c/65535) + 16.
+ * h_block_len (optional): every block's length, its size word included.  n == 0 writes nothing.
+ * QZD_ERR_PARAM: a NULL argument, mini_match outside {3, 4}, block_sz not a power of two in 1 KB .. 512 KB;
+ * QZD_ERR_UNSUPPORTED: level outside 1-12 (every level runs the same parse); QZD_ERR_DSTCAP: dst_cap below the bound. */
+uint64_t qzd_lz4s_bound(uint64_t n, uint32_t block_sz);
+int qzd_lz4s_compress_blocks(qzd_ctx *ctx, const uint8_t *d_src, uint64_t n, uint32_t block_sz, uint32_t mini_match,
+                             int level, uint8_t *d_dst, uint64_t dst_cap, uint64_t *h_out_len, uint32_t *h_block_len);
 /* decode nsegs frames (any block mode; block checksums and the content checksum verified on the GPU); replaces
  * LZ4F_decompress, src/qatzip_sw.c:496, and answers as it does: a wrong block checksum is a data error whether or not the
  * frame has a content checksum, and in a frame of independent blocks (FLG bit 5) a match that reaches in front of its own

@@ -70,6 +70,9 @@ def load(build_if_missing=True):
     L.qzd_lz4hc_compress_frames.argtypes = [vp, u8p, C.c_uint64, C.c_uint32, C.c_int, u8p, C.c_uint64, C.POINTER(C.c_uint64), vp]
     L.qzd_lz4hc_compress_frames_hw.argtypes = L.qzd_lz4hc_compress_frames.argtypes
     L.qzd_lz4hc_compress_linked.argtypes = [vp, u8p, C.c_uint64, C.c_int, u8p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.qzd_lz4s_bound.argtypes = [C.c_uint64, C.c_uint32]; L.qzd_lz4s_bound.restype = C.c_uint64
+    L.qzd_lz4s_compress_blocks.argtypes = [vp, u8p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, u8p, C.c_uint64,
+                                           C.POINTER(C.c_uint64), vp]
     L.qzd_chunk_lens.argtypes = [vp, vp, C.c_uint32]
     L.qzd_shard_root_create.argtypes = [vp, C.c_uint32, C.c_uint64, C.c_char_p, C.POINTER(vp)]
     L.qzd_shard_attach.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_char_p, C.c_uint64, C.POINTER(vp)]
@@ -118,6 +121,7 @@ def exported_symbols():
             "qzd_deflate_slots", "qzd_inflate_stream_to_host", "qzd_inflate_stream_from_host", "qzamd_async_stats", "qzd_shard_root_create",
             "qzd_shard_attach", "qzd_shard_slot_handle", "qzd_shard_attach_slot", "qzd_lz4_compress_linked", "qzd_shard_put", "qzd_shard_finish", "qzd_shard_close", "qzd_crc32_combine",
             "qzd_lz4hc_compress_frames", "qzd_lz4hc_compress_frames_hw", "qzd_lz4hc_compress_linked",
+            "qzd_lz4s_bound", "qzd_lz4s_compress_blocks",
             "qzd_crcn_ranges", "qzd_xxh32_ranges", "qzd_blocks_compress", "qzd_blocks_decompress",
             "qzd_crc32_fold", "qzd_pcie_peak", "qzd_rccl_unique_id", "qzd_rccl_create", "qzd_rccl_gather", "qzd_rccl_close"]
 
@@ -313,6 +317,15 @@ class Context:
             self._chk(self.L.qzd_lz4_compress_linked(self.h, d_src.ptr, n, d_dst.ptr, d_dst.nbytes, C.byref(ol)))
         return ol.value
 
+    def lz4s_compress_blocks(self, d_src, n, d_dst, block_sz=65536, mini_match=3, level=1, dst_cap=None):
+        """every block_sz bytes one LZ4s block (u32le size, LZ77 sequences) -> (out_len, per-block lengths with the size word)"""
+        nb = (n + block_sz - 1) // block_sz
+        ol = C.c_uint64(0)
+        lens = np.zeros(max(nb, 1), np.uint32)
+        self._chk(self.L.qzd_lz4s_compress_blocks(self.h, d_src.ptr, n, block_sz, mini_match, level, d_dst.ptr,
+                                                  d_dst.nbytes if dst_cap is None else dst_cap, C.byref(ol), lens.ctypes.data))
+        return ol.value, lens[:nb]
+
     LZ4D_ROUTES = {"auto": 0, "wave": 1, "blocks": 2}
 
     def lz4_decode_route(self, route):
@@ -340,3 +353,8 @@ def max_deflate_len(n, chunk_sz=65536):
     """worst-case raw stream size for n bytes (stored blocks + markers)"""
     nchunks = max(1, (n + chunk_sz - 1) // chunk_sz)
     return n + nchunks * (5 * (chunk_sz // 32767 + 2) + 16) + 64
+
+
+def lz4s_bound(n, block_sz=65536):
+    """what the LZ4s blocks of n bytes can grow to (qzd_lz4s_bound): per block of c bytes 4 + c + c/255 + 4*ceil(c/65535) + 16"""
+    return int(load().qzd_lz4s_bound(n, block_sz))

@@ -8,9 +8,10 @@ from ._lib import load
 
 QZ_OK, QZ_DUPLICATE, QZ_PARAMS, QZ_FAIL, QZ_BUF_ERROR, QZ_DATA_ERROR = 0, 1, -1, -2, -3, -4
 QZ_NOT_SUPPORTED, QZ_NOSW_NO_HW, QZ_UNSUPPORTED_FMT = -200, -101, 16
+QZ_POST_PROCESS_ERROR = -117
 QZ_METADATA_OVERFLOW, QZ_OUT_OF_RANGE = -118, -119
 QZ_DEFLATE_4B, QZ_DEFLATE_GZIP, QZ_DEFLATE_GZIP_EXT, QZ_DEFLATE_RAW = 0, 1, 2, 3
-QZ_DEFLATE, QZ_LZ4 = 8, ord("4")
+QZ_DEFLATE, QZ_LZ4, QZ_LZ4s = 8, ord("4"), ord("s")
 QZ_DIR_COMPRESS, QZ_DIR_DECOMPRESS, QZ_DIR_BOTH = 0, 1, 2
 COMMON_MEM, PINNED_MEM = 0, 1
 
@@ -45,6 +46,17 @@ class QzSessionParamsDeflateExt(C.Structure):
 
 class QzSessionParamsLZ4(C.Structure):
     _fields_ = [("common_params", QzSessionParamsCommon)]
+
+
+# qzLZ4SCallbackFn: int cb(void *external, const unsigned char *src, unsigned int *src_len, unsigned char *dest,
+#                          unsigned int *dest_len, int *ExtStatus)
+QzLZ4SCallback = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint), C.c_void_p, C.POINTER(C.c_uint),
+                             C.POINTER(C.c_int))
+
+
+class QzSessionParamsLZ4S(C.Structure):
+    _fields_ = [("common_params", QzSessionParamsCommon), ("qzCallback", QzLZ4SCallback), ("qzCallback_external", C.c_void_p),
+                ("lz4s_mini_match", C.c_uint)]
 
 
 class QzStream(C.Structure):
@@ -86,6 +98,11 @@ def lib():
         L.qzSetDefaults.argtypes = [P(QzSessionParams)]
         L.qzGetDefaultsDeflate.argtypes = [P(QzSessionParamsDeflate)]
         L.qzGetDefaultsLZ4.argtypes = [P(QzSessionParamsLZ4)]
+        L.qzSetupSessionLZ4S.argtypes = [P(QzSession), P(QzSessionParamsLZ4S)]
+        L.qzGetDefaultsLZ4S.argtypes = [P(QzSessionParamsLZ4S)]
+        L.qzSetDefaultsLZ4S.argtypes = [P(QzSessionParamsLZ4S)]
+        L.qzCompressExt.argtypes = [P(QzSession), u8p, up, C.c_void_p, up, C.c_uint, P(C.c_uint64)]
+        L.qzCompressCrcExt.argtypes = [P(QzSession), u8p, up, C.c_void_p, up, C.c_uint, P(C.c_ulong), P(C.c_uint64)]
         L.qzGetDefaultsDeflateExt.argtypes = [P(QzSessionParamsDeflateExt)]
         L.qzSetupSessionDeflateExt.argtypes = [P(QzSession), P(QzSessionParamsDeflateExt)]
         L.qzCompress.argtypes = [P(QzSession), u8p, up, C.c_void_p, up, C.c_uint]
@@ -166,10 +183,23 @@ class Session:
     """A QzSession_T set up the way test/main.c does it: qzGetDefaults -> tweak -> qzSetupSession."""
 
     def __init__(self, data_fmt=QZ_DEFLATE_GZIP_EXT, hw_buff_sz=65536, comp_lvl=1, lz4=False, strm_buff_sz=None,
-                 zlib_format=False, stop_at_stream_end=False):
+                 zlib_format=False, stop_at_stream_end=False, lz4s=False, mini_match=3, callback=None, external=None):
         self.L = lib()
         self.s = QzSession()
-        if zlib_format or stop_at_stream_end:  # qzSetupSessionDeflateExt: zlib_format = 1 is the RFC 1950 wrapper with an Adler-32 trailer
+        self.cb = None
+        if lz4s:
+            # an LZ4s session (qzSetupSessionLZ4S): compress only; callback is a Python callable with qzLZ4SCallbackFn's
+            # arguments (or a QzLZ4SCallback), kept alive by this object for as long as the session may call it
+            p = QzSessionParamsLZ4S(); self.L.qzGetDefaultsLZ4S(C.byref(p))
+            p.common_params.comp_algorithm = QZ_LZ4s; p.common_params.direction = QZ_DIR_COMPRESS
+            p.common_params.hw_buff_sz = hw_buff_sz; p.common_params.comp_lvl = comp_lvl
+            p.lz4s_mini_match = mini_match
+            if callback is not None:
+                self.cb = callback if isinstance(callback, QzLZ4SCallback) else QzLZ4SCallback(callback)
+                p.qzCallback = self.cb
+            p.qzCallback_external = external
+            self.rc_setup = self.L.qzSetupSessionLZ4S(C.byref(self.s), C.byref(p))
+        elif zlib_format or stop_at_stream_end:  # qzSetupSessionDeflateExt: zlib_format = 1 is the RFC 1950 wrapper with an Adler-32 trailer
             p = QzSessionParamsDeflateExt(); self.L.qzGetDefaultsDeflateExt(C.byref(p))
             if zlib_format:
                 p.deflate_params.data_fmt = QZ_DEFLATE_RAW; p.zlib_format = 1
@@ -202,6 +232,18 @@ class Session:
         crc = C.c_ulong(crc0)
         rc = self.L.qzCompressCrc(C.byref(self.s), src, C.byref(sl), dst, C.byref(dl), last, C.byref(crc))
         return rc, sl.value, dst.raw[:dl.value], crc.value
+
+    def compress_ext(self, src, last=1, cap=None):
+        """qzCompressExt -> (rc, consumed, out_bytes, ext_rc); src: bytes or a ctypes buffer (whose address the callback of an
+        LZ4s session then sees)"""
+        n = len(src)
+        if cap is None:
+            cap = self.L.qzMaxCompressedLength(max(n, 1), C.byref(self.s)) + 64
+        sl, dl, ext = C.c_uint(n), C.c_uint(cap), C.c_uint64(7)
+        dst = C.create_string_buffer(max(cap, 1))
+        a = src if isinstance(src, bytes) else C.cast(src, C.c_char_p)
+        rc = self.L.qzCompressExt(C.byref(self.s), a, C.byref(sl), dst, C.byref(dl), last, C.byref(ext))
+        return rc, sl.value, dst.raw[:dl.value], ext.value
 
     def decompress(self, comp: bytes, cap: int, crc0=0, want_crc=False):
         """-> (rc, consumed, out_bytes[, crc]): qzDecompress, or qzDecompressCrc (running CRC-32 of the output) with want_crc"""

@@ -147,6 +147,17 @@ static int lz4_to(Params &p, const QzSessionParamsLZ4_T *s)
     p.fmt = F_LZ4;
     return check_common(p, true);
 }
+/* qzCheckParamsLZ4S, src/qatzip_utils.c:604-635 */
+static int lz4s_to(Params &p, const QzSessionParamsLZ4S_T *s)
+{
+    if (s->common_params.comp_algorithm != QZ_LZ4s || s->common_params.direction != QZ_DIR_COMPRESS) return QZ_PARAMS;
+    if (s->lz4s_mini_match < 3 || s->lz4s_mini_match > 4) return QZ_PARAMS;
+    p = g_def;
+    from_common(p, s->common_params);
+    p.fmt = F_LZ4S;
+    p.cb = s->qzCallback; p.cb_ext = s->qzCallback_external; p.lz4s_mini_match = s->lz4s_mini_match;
+    return check_common(p, true);
+}
 
 extern "C" int qzGetDefaults(QzSessionParams_T *d)
 {
@@ -220,7 +231,13 @@ extern "C" int qzSetDefaultsLZ4(QzSessionParamsLZ4_T *d)
     pthread_mutex_lock(&g_lock); g_def = p; pthread_mutex_unlock(&g_lock);
     return QZ_OK;
 }
-extern "C" int qzSetDefaultsLZ4S(QzSessionParamsLZ4S_T *d) { (void)d; return QZ_NOT_SUPPORTED; }
+extern "C" int qzSetDefaultsLZ4S(QzSessionParamsLZ4S_T *d)
+{
+    Params p;
+    if (!d || lz4s_to(p, d) != QZ_OK) return QZ_PARAMS;
+    pthread_mutex_lock(&g_lock); g_def = p; pthread_mutex_unlock(&g_lock);
+    return QZ_OK;
+}
 
 /* ------------------------------------------------------------------ init / sessions */
 extern "C" int qzInit(QzSession_T *sess, unsigned char sw_backup)
@@ -298,9 +315,13 @@ extern "C" int qzSetupSessionLZ4(QzSession_T *sess, QzSessionParamsLZ4_T *params
 }
 extern "C" int qzSetupSessionLZ4S(QzSession_T *sess, QzSessionParamsLZ4S_T *params)
 {
-    (void)params;
+    QzSessionParamsLZ4S_T tmp; Params p;
     if (!sess) return QZ_PARAMS;
-    return QZ_NOT_SUPPORTED;        /* LZ4s is a QAT-2.0 hardware format with no software path in the reference */
+    /* the current defaults, checked like a caller's (src/qatzip.c:1314-1321): the factory's direction is QZ_DIR_BOTH, so
+     * without a qzSetDefaultsLZ4S before it a NULL here is QZ_PARAMS, as in the reference */
+    if (!params) { qzGetDefaultsLZ4S(&tmp); params = &tmp; }
+    if (lz4s_to(p, params) != QZ_OK) return QZ_PARAMS;
+    return make_session(sess, p);
 }
 
 static void async_drain(QzSession_T *sess);   /* queued qzCompress2/qzDecompress2 requests of a session finish first */
@@ -595,6 +616,43 @@ static int compress_lz4_hw(QzSession_T *sess, Sess *s, const unsigned char *src,
     return take == nchunks ? QZ_OK : QZ_BUF_ERROR;
 }
 
+/* LZ4s sessions (src/qatzip.c:1304-1337; block header src/qatzip_lz4.c:219-231, no footer): every hw_buff_sz chunk of the
+ * call is one block - u32le size, LZ77 sequences ("LZ4s sessions") - for the session's post-processing
+ * callback.  Whole blocks that fit, QZ_BUF_ERROR with progress otherwise, as compress_lz4_hw.  Every call goes to the GPU:
+ * there is no software LZ4s compressor to send a small one to. */
+static int compress_lz4s(QzSession_T *sess, Sess *s, const unsigned char *src, unsigned int *src_len,
+                         unsigned char *dest, unsigned int *dest_len, unsigned long *crc)
+{
+    const uint32_t n = *src_len, cap = *dest_len, hw = s->p.hw_buff_sz;
+    *src_len = 0; *dest_len = 0;
+    if (n == 0) return QZ_OK;
+    const uint32_t nchunks = (n + hw - 1) / hw;
+    const uint64_t bound = qzd_lz4s_bound(n, hw);
+    int rc = reserve(s, n, bound + 64);
+    if (rc) return rc;
+    if (qzd_h2d(s->ctx, s->d_in, src, n) != QZD_OK) return QZ_FAIL;
+    std::vector<uint32_t> lens(nchunks);
+    uint64_t produced = 0;
+    if (qzd_lz4s_compress_blocks(s->ctx, s->d_in, n, hw, s->p.lz4s_mini_match, (int)s->p.comp_lvl, s->d_out, s->out_cap, &produced,
+                                 lens.data()) != QZD_OK) {
+        logmsg(LOG_ERROR, "GPU LZ4s failed: %s\n", qzd_last_error(s->ctx));
+        return QZ_FAIL;
+    }
+    uint32_t take = 0; uint64_t bytes = 0;
+    while (take < nchunks && bytes + lens[take] <= cap) bytes += lens[take++];
+    if (take == 0) return QZ_BUF_ERROR;
+    if (qzd_d2h(s->ctx, dest, s->d_out, bytes) != QZD_OK) return QZ_FAIL;
+    const uint32_t used = take == nchunks ? n : take * hw;
+    if (crc) {
+        uint32_t c = 0;
+        if (qzd_crc32(s->ctx, s->d_in, used, &c) != QZD_OK) return QZ_FAIL;
+        *crc = qzd_crc32_combine((uint32_t)*crc, c, used);
+    }
+    *src_len = used; *dest_len = (unsigned int)bytes;
+    sess->total_in += used; sess->total_out += bytes;              /* LZ4s bytes, before post-processing (src/qatzip.c:2064-2065) */
+    return take == nchunks ? QZ_OK : QZ_BUF_ERROR;
+}
+
 /* LZ4 sessions: one frame per call, `last` ignored (src/qatzip_sw.c:443-471) */
 static int compress_lz4(QzSession_T *sess, Sess *s, const unsigned char *src, unsigned int *src_len,
                         unsigned char *dest, unsigned int *dest_len)
@@ -714,7 +772,24 @@ static int compress_direct(QzSession_T *sess, const unsigned char *src, unsigned
     }
     if (s->p.fmt == F_LZ4 && s->hw_framing && *src_len >= s->p.input_sz_thrshold) rc = compress_lz4_hw(sess, s, src, src_len, dest, dest_len);
     else if (s->p.fmt == F_LZ4) rc = compress_lz4(sess, s, src, src_len, dest, dest_len);
-    else if (s->p.fmt == F_LZ4S) rc = QZ_UNSUPPORTED_FMT;
+    /* qzCompress2 and the Crc64 calls (may_queue false: the queue's consumer, or a caller that needs this session's device
+     * copy) answer for an LZ4s session what they always did: the callback belongs to the four qzCompress calls */
+    else if (s->p.fmt == F_LZ4S && !may_queue) rc = QZ_UNSUPPORTED_FMT;
+    else if (s->p.fmt == F_LZ4S) {
+        rc = compress_lz4s(sess, s, src, src_len, dest, dest_len, crc);
+        /* the post-processing callback, on the caller's thread, with the lengths as just set (src/qatzip.c:1804-1839): it may
+         * rewrite dest and *dest_len; anything but QZ_OK from it is the call's answer, its ExtStatus the call's ext_rc */
+        if (s->p.cb && *src_len != 0 && (rc == QZ_OK || rc == QZ_BUF_ERROR)) {
+            int ext_status = 0;
+            const int cb_rc = s->p.cb(s->p.cb_ext, src, src_len, dest, dest_len, &ext_status);
+            if (cb_rc != QZ_OK) {
+                if (ext_rc) *ext_rc = (uint64_t)ext_status;
+                rc = cb_rc;
+                sess->thd_sess_stat = rc;
+                goto fail;
+            }
+        }
+    }
     /* the reference sends a call below input_sz_thrshold to its software path even on a QAT box (src/qatzip.c:1934-1947):
      * such a call - an empty one included - keeps the software path's framing */
     else if (s->hw_framing && !s->open && *src_len >= s->p.input_sz_thrshold &&
@@ -998,6 +1073,12 @@ extern "C" unsigned int qzMaxCompressedLength(unsigned int src_sz, QzSession_T *
     uint64_t out = ((uint64_t)9 * src_sz + 7) / 8 + QZ_SKID_PAD_SZ + (24 + 8);
     if (sess && sess->internal && ((Sess *)sess->internal)->p.fmt == F_LZ4)
         out = (uint64_t)src_sz + 27 + 4 * ((uint64_t)src_sz / 65536 + 1) + src_sz / 255;
+    /* LZ4s: the sum over the call's hw_buff_sz chunks of 4 + c + c/255 + 4*ceil(c/65535) + 16 per chunk of c bytes.  All
+     * literals is the worst case - the compressor takes no match that costs more than it covers (qzk_lz4s.h) - and c
+     * literals are ceil(c/65535) runs: a token, 257 length bytes and two offset bytes per full run (c/255 pays 257 of them,
+     * the 4 per run the rest), the last run without offset; 4 for the size word, 16 to spare. */
+    if (sess && sess->internal && ((Sess *)sess->internal)->p.fmt == F_LZ4S)
+        out = qzd_lz4s_bound(src_sz, ((Sess *)sess->internal)->p.hw_buff_sz);
     return (out >> 32) ? 0 : (unsigned int)out;
 }
 
@@ -1862,8 +1943,8 @@ fail:
 }
 
 /* ------------------------------------------------------------------ declared-only surface
- * what is left of it: LZ4s (qzSetupSessionLZ4S / qzSetDefaultsLZ4S above, QAT-2.0 silicon only) answers QZ_NOT_SUPPORTED;
- * the two version queries below answer for this library */
+ * nothing of it is left (LZ4s sessions compress on the GPU since K4s: qzSetupSessionLZ4S / compress_lz4s above); the two
+ * version queries below answer for this library */
 extern "C" int qzGetSoftwareComponentCount(unsigned int *n) { if (!n) return QZ_PARAMS; *n = 1; return QZ_OK; }
 extern "C" int qzGetSoftwareComponentVersionList(QzSoftwareVersionInfo_T *info, unsigned int *n)
 {

@@ -1250,6 +1250,61 @@ extern "C" int qzd_lz4hc_compress_linked(qzd_ctx *c, const uint8_t *d_src, uint6
     return lz4hc_impl(c, d_src, n, (uint32_t)n, level, 0, d_dst, dst_cap, h_out_len, NULL);
 }
 
+/* ------------------------------------------------------------------ LZ4s blocks (K4s) */
+#include "qzk_lz4s.h"
+#define QZD_L4S_WPC 10u             /* waves a CU holds: 16 KiB of LDS each (qzk_lz4s.h) */
+
+/* per block of c bytes 4 + c + c/255 + 4*ceil(c/65535) + 16.  Proof: all literals is the worst case.  A sequence with a
+ * match is only taken when it is no longer than the bytes it covers plus one per 255 of them (qzk_l4s_block), so what
+ * remains to pay for is literals: runs of 65535 cost a token, 257 length bytes and two offset bytes (c/255 pays 257 of
+ * them, the 4 per started run the rest), the last run a token and at most 257 length bytes; 4 for the size word. */
+extern "C" uint64_t qzd_lz4s_bound(uint64_t n, uint32_t block_sz)
+{
+    if (!block_sz) return 0;
+    const uint64_t full = n / block_sz, rest = n % block_sz;
+    return full * QZK_L4S_BOUND(block_sz) + (rest ? QZK_L4S_BOUND((uint32_t)rest) : 0);
+}
+
+extern "C" int qzd_lz4s_compress_blocks(qzd_ctx *c, const uint8_t *d_src, uint64_t n, uint32_t block_sz, uint32_t mini_match,
+                                        int level, uint8_t *d_dst, uint64_t dst_cap, uint64_t *h_out_len, uint32_t *h_block_len)
+{
+    if (!c || !d_dst || (n && !d_src) || !h_out_len) return QZD_ERR_PARAM;
+    if (mini_match < 3 || mini_match > 4 || block_sz < QZK_L4S_MINBLK || block_sz > QZK_L4S_MAXBLK || (block_sz & (block_sz - 1))) {
+        snprintf(c->err, sizeof(c->err), "LZ4s: mini_match 3 or 4, block_sz a power of two in 1 KB .. 512 KB");
+        return QZD_ERR_PARAM;
+    }
+    if (level < 1 || level > 12) { snprintf(c->err, sizeof(c->err), "LZ4s: levels 1-12 (level %d asked for)", level); return QZD_ERR_UNSUPPORTED; }
+    if ((n + block_sz - 1) / block_sz > 0x7fffffffull) { snprintf(c->err, sizeof(c->err), "LZ4s: too many blocks"); return QZD_ERR_UNSUPPORTED; }
+    if (dst_cap < qzd_lz4s_bound(n, block_sz)) { snprintf(c->err, sizeof(c->err), "destination too small"); return QZD_ERR_DSTCAP; }
+    *h_out_len = 0;
+    if (!n) return QZD_OK;
+    hipSetDevice(c->device);
+    const uint32_t nb = (uint32_t)((n + block_sz - 1) / block_sz);
+    const uint32_t stride = (QZK_L4S_BOUND(block_sz) + 15) & ~15u;
+    QZD_TRY(reserve_call_arrays(c, nb));
+    uint32_t batch = nb < 16384u ? nb : 16384u;
+    if ((uint64_t)batch * stride > (1ull << 30)) batch = (uint32_t)((1ull << 30) / stride);       /* slots of a gigabyte at most */
+    QZD_TRY(grow_dev(c, (void **)&c->lz4_slots, &c->slot_cap, (size_t)batch * stride));
+    uint8_t *const slots = c->lz4_slots;
+    hipStream_t st = c->st[0];
+    const uint32_t cus = c->cus ? c->cus : 256u;
+    QZD_TRY(call_begin(c, st, nb, c->nbatches));
+    for (uint32_t b = 0; b < nb; b += batch) {
+        const uint32_t bn = nb - b < batch ? nb - b : batch;
+        const uint64_t boff = (uint64_t)b * block_sz;
+        /* persistent waves, as many as the device holds at once, pull the round's blocks from the stream's counter */
+        HIPCHK(c, hipMemsetAsync(c->k1_counter, 0, 4, st));
+        hipLaunchKernelGGL(qzk_lz4s_pull_kernel, dim3(std::min<uint32_t>(bn, QZD_L4S_WPC * cus)), dim3(64), 0, st, d_src + boff, n - boff,
+                           block_sz, bn, slots, stride, c->d_len + b, mini_match, c->k1_counter);
+        launch_scan_gather(c, st, slots, stride, b, bn, d_dst, dst_cap);
+    }
+    HIPCHK(c, hipEventRecord(c->ev_end, st));
+    QZD_TRY(publish_totals(c, st));
+    QZD_TRY(finish_sync_call(c, st, h_out_len));
+    if (h_block_len) HIPCHK(c, hipMemcpy(h_block_len, c->d_len, (size_t)nb * 4, hipMemcpyDeviceToHost));
+    return QZD_OK;
+}
+
 /* 0 auto, 1 every frame on one wave (qzk_lz4d_kernel), 2 a wave per block for every candidate frame that qualifies */
 extern "C" int qzd_lz4_decode_route(qzd_ctx *c, int route)
 {
