@@ -267,6 +267,24 @@ int qzd_lz4hc_compress_linked(qzd_ctx *ctx, const uint8_t *d_src, uint64_t n, in
 uint64_t qzd_lz4s_bound(uint64_t n, uint32_t block_sz);
 int qzd_lz4s_compress_blocks(qzd_ctx *ctx, const uint8_t *d_src, uint64_t n, uint32_t block_sz, uint32_t mini_match,
                              int level, uint8_t *d_dst, uint64_t dst_cap, uint64_t *h_out_len, uint32_t *h_block_len);
+/* zstd frames (RFC 8878; the subset is in INTEGRATION.md, "Zstd sessions"): every block_sz bytes of d_src become one frame of
+ * one block, back to back in d_dst - the LZ4s parse and the entropy stage in one kernel, a wave per chunk (Kz, qzk_zstd.h).
+ * qzd_zstd_bound: what the frames of n bytes can grow to - per chunk of c bytes 4 + 1 + 4 + 3 + c (the Raw block).
+ * h_frame_len (optional): every frame's length.  n == 0 writes nothing.  Arguments and error codes as
+ * qzd_lz4s_compress_blocks, but block_sz is a power of two in 1 KB .. 128 KB. */
+uint64_t qzd_zstd_bound(uint64_t n, uint32_t block_sz);
+int qzd_zstd_compress_frames(qzd_ctx *ctx, const uint8_t *d_src, uint64_t n, uint32_t block_sz, uint32_t mini_match,
+                             int level, uint8_t *d_dst, uint64_t dst_cap, uint64_t *h_out_len, uint32_t *h_frame_len);
+/* the entropy stage alone, for a caller with a parse of its own (what ZSTD_compressSequences is to libzstd): frame i is
+ * h_desc[3i] bytes of content (1 .. 128 KB) made of h_desc[3i + 1] records and h_desc[3i + 2] literal bytes; d_seqs holds the
+ * records of all frames back to back - three uint32 each: literal length, match length, offset - and d_literals their
+ * literals, trailing ones included.  dst_cap must hold the sum over the frames of content + 12.
+ * QZD_ERR_PARAM: a NULL argument, a content size of 0 or above 128 KB, more literals than content, more records than a
+ * third of what the matches cover; QZD_ERR_DATA (nothing is delivered, *h_out_len = 0): a match shorter than 3, an offset
+ * that is 0 or beyond the bytes produced before its match, lengths that do not add up to the content size;
+ * QZD_ERR_DSTCAP: dst_cap below the bound. */
+int qzd_zstd_encode_frames(qzd_ctx *ctx, const uint8_t *d_literals, const uint32_t *d_seqs, const uint32_t *h_desc,
+                           uint32_t nframes, uint8_t *d_dst, uint64_t dst_cap, uint64_t *h_out_len, uint32_t *h_frame_len);
 /* decode nsegs frames (any block mode; block checksums and the content checksum verified on the GPU); replaces
  * LZ4F_decompress, src/qatzip_sw.c:496, and answers as it does: a wrong block checksum is a data error whether or not the
  * frame has a content checksum, and in a frame of independent blocks (FLG bit 5) a match that reaches in front of its own

@@ -14,7 +14,9 @@ def _sources():
         if f.endswith((".hip", ".cpp", ".c", ".h")):
             out.append(os.path.join(CSRC, f))
     out.append(os.path.join(HERE, "cli", "qzip_amd.c"))
+    out.append(os.path.join(HERE, "cli", "qzstd_amd.c"))
     out.append(os.path.join(os.path.dirname(HERE), "include", "qzamd_device.h"))
+    out.append(os.path.join(os.path.dirname(HERE), "include", "qzamd_zstd.h"))
     q = os.path.join(os.path.dirname(HERE), "include", "qatzip.h")
     if os.path.exists(q):
         out.append(q)
@@ -22,7 +24,7 @@ def _sources():
 
 
 def needs_build():
-    if not os.path.exists(SO) or not os.path.exists(os.path.join(HERE, "qzip-amd")):
+    if not os.path.exists(SO) or not os.path.exists(CLI) or not os.path.exists(ZSTD_CLI):
         return True
     t = os.path.getmtime(SO)
     return any(os.path.getmtime(s) > t for s in _sources())
@@ -47,12 +49,19 @@ def build(force=False, verbose=False):
 
 
 CLI = os.path.join(HERE, "qzip-amd")
+ZSTD_CLI = os.path.join(HERE, "qzstd-amd")
 
 
 def build_cli(verbose=False):
     """the qzip-style file front end: plain C against include/qatzip.h, linked like any application"""
     cmd = ["gcc", "-O2", "-std=gnu99", "-Wall", "-I", os.path.join(os.path.dirname(HERE), "include"),
            os.path.join(HERE, "cli", "qzip_amd.c"), "-o", CLI, "-L", HERE, "-lqatzip_amd", "-Wl,-rpath,$ORIGIN"]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
+    # qzstd-amd: the compress path of the reference's qzstd on a zstd session (include/qzamd_zstd.h)
+    cmd = ["gcc", "-O2", "-std=gnu99", "-Wall", "-I", os.path.join(os.path.dirname(HERE), "include"),
+           os.path.join(HERE, "cli", "qzstd_amd.c"), "-o", ZSTD_CLI, "-L", HERE, "-lqatzip_amd", "-Wl,-rpath,$ORIGIN"]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)

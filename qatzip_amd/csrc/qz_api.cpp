@@ -32,6 +32,7 @@
 
 #include "../../include/qatzip.h"
 #include "../../include/qzamd_device.h"
+#include "../../include/qzamd_zstd.h"
 
 enum { F_4B = 0, F_GZIP, F_GZIP_EXT, F_RAW, F_LZ4, F_LZ4S, F_ZLIB };   /* DataFormatInternal_T order, src/qatzip_internal.h:238-253 */
 
@@ -40,6 +41,7 @@ struct Params {
     unsigned max_forks; unsigned char sw_backup; unsigned hw_buff_sz, strm_buff_sz, input_sz_thrshold,
     req_cnt_thrshold, wait_cnt_thrshold; QzPollingMode_T polling_mode; unsigned is_sensitive_mode;
     unsigned char stop_at_stream_end, zlib_format; qzLZ4SCallbackFn cb; void *cb_ext; unsigned lz4s_mini_match;
+    bool zstd;                      /* an F_LZ4S session made by qzSetupSessionZstdAMD: the same parse, written as zstd frames */
 };
 
 struct Sess {
@@ -154,7 +156,7 @@ static int lz4s_to(Params &p, const QzSessionParamsLZ4S_T *s)
     if (s->lz4s_mini_match < 3 || s->lz4s_mini_match > 4) return QZ_PARAMS;
     p = g_def;
     from_common(p, s->common_params);
-    p.fmt = F_LZ4S;
+    p.fmt = F_LZ4S; p.zstd = false;
     p.cb = s->qzCallback; p.cb_ext = s->qzCallback_external; p.lz4s_mini_match = s->lz4s_mini_match;
     return check_common(p, true);
 }
@@ -321,6 +323,20 @@ extern "C" int qzSetupSessionLZ4S(QzSession_T *sess, QzSessionParamsLZ4S_T *para
      * without a qzSetDefaultsLZ4S before it a NULL here is QZ_PARAMS, as in the reference */
     if (!params) { qzGetDefaultsLZ4S(&tmp); params = &tmp; }
     if (lz4s_to(p, params) != QZ_OK) return QZ_PARAMS;
+    return make_session(sess, p);
+}
+
+/* a zstd session (include/qzamd_zstd.h): an LZ4s session's checks, and on top of them no hw_buff_sz above one zstd block
+ * (the reference's qzstd: MAX_BLOCK_SIZE 128 KB, one ZSTD_compressSequences call per chunk) and no callback - the frames
+ * are what the reference's callback makes, there is nothing left to post-process */
+extern "C" int qzSetupSessionZstdAMD(QzSession_T *sess, QzSessionParamsLZ4S_T *params)
+{
+    QzSessionParamsLZ4S_T tmp; Params p;
+    if (!sess) return QZ_PARAMS;
+    if (!params) { qzGetDefaultsLZ4S(&tmp); params = &tmp; }
+    if (lz4s_to(p, params) != QZ_OK) return QZ_PARAMS;
+    if (p.hw_buff_sz > 128 * 1024 || p.cb) return QZ_PARAMS;
+    p.zstd = true;
     return make_session(sess, p);
 }
 
@@ -627,15 +643,16 @@ static int compress_lz4s(QzSession_T *sess, Sess *s, const unsigned char *src, u
     *src_len = 0; *dest_len = 0;
     if (n == 0) return QZ_OK;
     const uint32_t nchunks = (n + hw - 1) / hw;
-    const uint64_t bound = qzd_lz4s_bound(n, hw);
+    const uint64_t bound = s->p.zstd ? qzd_zstd_bound(n, hw) : qzd_lz4s_bound(n, hw);
     int rc = reserve(s, n, bound + 64);
     if (rc) return rc;
     if (qzd_h2d(s->ctx, s->d_in, src, n) != QZD_OK) return QZ_FAIL;
     std::vector<uint32_t> lens(nchunks);
     uint64_t produced = 0;
-    if (qzd_lz4s_compress_blocks(s->ctx, s->d_in, n, hw, s->p.lz4s_mini_match, (int)s->p.comp_lvl, s->d_out, s->out_cap, &produced,
-                                 lens.data()) != QZD_OK) {
-        logmsg(LOG_ERROR, "GPU LZ4s failed: %s\n", qzd_last_error(s->ctx));
+    /* a zstd session: the same chunks, the same parse, a frame each instead of a block */
+    if ((s->p.zstd ? qzd_zstd_compress_frames : qzd_lz4s_compress_blocks)(s->ctx, s->d_in, n, hw, s->p.lz4s_mini_match, (int)s->p.comp_lvl,
+                                                                          s->d_out, s->out_cap, &produced, lens.data()) != QZD_OK) {
+        logmsg(LOG_ERROR, "GPU %s failed: %s\n", s->p.zstd ? "zstd" : "LZ4s", qzd_last_error(s->ctx));
         return QZ_FAIL;
     }
     uint32_t take = 0; uint64_t bytes = 0;
@@ -1079,6 +1096,9 @@ extern "C" unsigned int qzMaxCompressedLength(unsigned int src_sz, QzSession_T *
      * the 4 per run the rest), the last run without offset; 4 for the size word, 16 to spare. */
     if (sess && sess->internal && ((Sess *)sess->internal)->p.fmt == F_LZ4S)
         out = qzd_lz4s_bound(src_sz, ((Sess *)sess->internal)->p.hw_buff_sz);
+    /* a zstd session: per chunk the Raw block, 4 + 1 + 4 + 3 + c */
+    if (sess && sess->internal && ((Sess *)sess->internal)->p.fmt == F_LZ4S && ((Sess *)sess->internal)->p.zstd)
+        out = qzd_zstd_bound(src_sz, ((Sess *)sess->internal)->p.hw_buff_sz);
     return (out >> 32) ? 0 : (unsigned int)out;
 }
 

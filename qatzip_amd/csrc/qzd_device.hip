@@ -1305,6 +1305,109 @@ extern "C" int qzd_lz4s_compress_blocks(qzd_ctx *c, const uint8_t *d_src, uint64
     return QZD_OK;
 }
 
+/* ------------------------------------------------------------------ zstd frames (Kz) */
+#include "qzk_zstd.h"
+#include "qzd_zstd_host.h"
+#define QZD_ZS_WPC 9u               /* waves a CU holds: 17.7 KiB of LDS each (qzk_zstd.h) */
+
+/* per chunk of c bytes 4 + 1 + 4 + 3 + c: a block that would not be smaller than the chunk is written Raw */
+extern "C" uint64_t qzd_zstd_bound(uint64_t n, uint32_t block_sz) { return qzd_zs_bound(n, block_sz); }
+
+extern "C" int qzd_zstd_compress_frames(qzd_ctx *c, const uint8_t *d_src, uint64_t n, uint32_t block_sz, uint32_t mini_match,
+                                        int level, uint8_t *d_dst, uint64_t dst_cap, uint64_t *h_out_len, uint32_t *h_frame_len)
+{
+    if (!c || !d_dst || (n && !d_src) || !h_out_len) return QZD_ERR_PARAM;
+    if (!qzd_zs_params_ok(block_sz, mini_match)) {
+        snprintf(c->err, sizeof(c->err), "zstd: mini_match 3 or 4, block_sz a power of two in 1 KB .. 128 KB");
+        return QZD_ERR_PARAM;
+    }
+    if (level < 1 || level > 12) { snprintf(c->err, sizeof(c->err), "zstd: levels 1-12 (level %d asked for)", level); return QZD_ERR_UNSUPPORTED; }
+    if ((n + block_sz - 1) / block_sz > 0x7fffffffull) { snprintf(c->err, sizeof(c->err), "zstd: too many frames"); return QZD_ERR_UNSUPPORTED; }
+    if (dst_cap < qzd_zs_bound(n, block_sz)) { snprintf(c->err, sizeof(c->err), "destination too small"); return QZD_ERR_DSTCAP; }
+    *h_out_len = 0;
+    if (!n) return QZD_OK;
+    hipSetDevice(c->device);
+    const uint32_t nb = (uint32_t)((n + block_sz - 1) / block_sz);
+    const uint32_t stride = qzd_zs_stride(block_sz);
+    QZD_TRY(reserve_call_arrays(c, nb));
+    uint32_t batch = nb < 16384u ? nb : 16384u;
+    if ((uint64_t)batch * stride > (1ull << 30)) batch = (uint32_t)((1ull << 30) / stride);       /* slots of a gigabyte at most */
+    QZD_TRY(grow_dev(c, (void **)&c->lz4_slots, &c->slot_cap, (size_t)batch * stride));
+    /* records and literals per WAVE, not per chunk: a wave codes the chunk it parsed before it pulls the next */
+    const uint32_t cus = c->cus ? c->cus : 256u;
+    const uint32_t waves = std::min<uint32_t>(batch, QZD_ZS_WPC * cus);
+    QZD_TRY(grow_dev(c, (void **)&c->d_lane, &c->lane_cap, (size_t)waves * QZK_ZS_WAVEB(block_sz)));
+    uint8_t *const slots = c->lz4_slots;
+    hipStream_t st = c->st[0];
+    QZD_TRY(call_begin(c, st, nb, c->nbatches));
+    for (uint32_t b = 0; b < nb; b += batch) {
+        const uint32_t bn = nb - b < batch ? nb - b : batch;
+        const uint64_t boff = (uint64_t)b * block_sz;
+        HIPCHK(c, hipMemsetAsync(c->k1_counter, 0, 4, st));
+        hipLaunchKernelGGL(qzk_zstd_pull_kernel, dim3(std::min<uint32_t>(bn, waves)), dim3(64), 0, st, d_src + boff, n - boff,
+                           block_sz, bn, slots, stride, c->d_len + b, mini_match, c->k1_counter, c->d_lane);
+        launch_scan_gather(c, st, slots, stride, b, bn, d_dst, dst_cap);
+    }
+    HIPCHK(c, hipEventRecord(c->ev_end, st));
+    QZD_TRY(publish_totals(c, st));
+    QZD_TRY(finish_sync_call(c, st, h_out_len));
+    if (h_frame_len) HIPCHK(c, hipMemcpy(h_frame_len, c->d_len, (size_t)nb * 4, hipMemcpyDeviceToHost));
+    return QZD_OK;
+}
+
+extern "C" int qzd_zstd_encode_frames(qzd_ctx *c, const uint8_t *d_literals, const uint32_t *d_seqs, const uint32_t *h_desc,
+                                      uint32_t nframes, uint8_t *d_dst, uint64_t dst_cap, uint64_t *h_out_len, uint32_t *h_frame_len)
+{
+    if (!c || !d_dst || !h_out_len || (nframes && (!h_desc || !d_literals || !d_seqs))) return QZD_ERR_PARAM;
+    *h_out_len = 0;
+    if (!nframes) return QZD_OK;
+    if (nframes > 0x7fffffffu / 2) { snprintf(c->err, sizeof(c->err), "zstd: too many frames"); return QZD_ERR_UNSUPPORTED; }
+    std::vector<qzk_zs_fdesc> fd(nframes);
+    uint32_t maxc = 0;
+    if (!qzd_zs_describe(h_desc, nframes, fd.data(), &maxc, NULL, NULL)) {
+        snprintf(c->err, sizeof(c->err), "zstd: a frame holds 1 byte .. 128 KB, its literals at most that, a record at least three bytes");
+        return QZD_ERR_PARAM;
+    }
+    uint64_t bound = 0;
+    for (uint32_t i = 0; i < nframes; i++) bound += QZK_ZS_BOUND(fd[i].content);
+    if (dst_cap < bound) { snprintf(c->err, sizeof(c->err), "destination too small"); return QZD_ERR_DSTCAP; }
+    hipSetDevice(c->device);
+    const uint32_t stride = qzd_zs_stride(maxc);
+    QZD_TRY(reserve_call_arrays(c, nframes));
+    uint32_t batch = nframes < 16384u ? nframes : 16384u;
+    if ((uint64_t)batch * stride > (1ull << 30)) batch = (uint32_t)((1ull << 30) / stride);
+    QZD_TRY(grow_dev(c, (void **)&c->lz4_slots, &c->slot_cap, (size_t)batch * stride));
+    /* d_lane: the descriptions, then the word a wave sets when it meets records that are not a frame's */
+    const size_t descb = ((size_t)nframes * sizeof(qzk_zs_fdesc) + 15) & ~(size_t)15;
+    QZD_TRY(grow_dev(c, (void **)&c->d_lane, &c->lane_cap, descb + 16));
+    qzk_zs_fdesc *d_fd = (qzk_zs_fdesc *)c->d_lane;
+    uint32_t *d_bad = (uint32_t *)(c->d_lane + descb);
+    hipStream_t st = c->st[0];
+    const uint32_t cus = c->cus ? c->cus : 256u;
+    QZD_TRY(call_begin(c, st, nframes, c->nbatches));
+    HIPCHK(c, hipMemcpyAsync(d_fd, fd.data(), (size_t)nframes * sizeof(qzk_zs_fdesc), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemsetAsync(d_bad, 0, 4, st));
+    for (uint32_t b = 0; b < nframes; b += batch) {
+        const uint32_t bn = nframes - b < batch ? nframes - b : batch;
+        HIPCHK(c, hipMemsetAsync(c->k1_counter, 0, 4, st));
+        hipLaunchKernelGGL(qzk_zstd_encode_kernel, dim3(std::min<uint32_t>(bn, QZD_ZS_WPC * cus)), dim3(64), 0, st, d_literals,
+                           (const qzk_zs_seq *)d_seqs, d_fd + b, bn, c->lz4_slots, stride, c->d_len + b, d_bad, c->k1_counter);
+        launch_scan_gather(c, st, c->lz4_slots, stride, b, bn, d_dst, dst_cap);
+    }
+    HIPCHK(c, hipEventRecord(c->ev_end, st));
+    QZD_TRY(publish_totals(c, st));
+    uint32_t bad = 0;
+    HIPCHK(c, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st));       /* fd outlives the copy: finish_sync_call waits for st */
+    QZD_TRY(finish_sync_call(c, st, h_out_len));
+    if (bad) {
+        *h_out_len = 0;
+        snprintf(c->err, sizeof(c->err), "zstd: records that are not a frame's (lengths, an offset, or a match below 3)");
+        return QZD_ERR_DATA;
+    }
+    if (h_frame_len) HIPCHK(c, hipMemcpy(h_frame_len, c->d_len, (size_t)nframes * 4, hipMemcpyDeviceToHost));
+    return QZD_OK;
+}
+
 /* 0 auto, 1 every frame on one wave (qzk_lz4d_kernel), 2 a wave per block for every candidate frame that qualifies */
 extern "C" int qzd_lz4_decode_route(qzd_ctx *c, int route)
 {

@@ -46,7 +46,7 @@
  * That costs ratio only (text: 1.06 of liblz4's level-1 size, 1.10 allowed).
  *
  * The bound (qzd_lz4s_bound): a sequence with a match is taken only when it is no longer than what it covers plus one byte
- * per 255 covered (qzk_l4s_block, `the rule`), so all literals is the worst case.
+ * per 255 covered (qzk_l4s_parse, `the rule`), so all literals is the worst case.
  */
 #ifndef QZK_LZ4S_H
 #define QZK_LZ4S_H
@@ -125,13 +125,25 @@ QZ_DEV uint32_t qzk_l4s_tail(uint8_t *out, uint32_t op, const uint8_t *lit, uint
     return qzk_l4s_put(out, op, lit, L, 0, 0, true, lane);
 }
 
-/* the sequences of in[0..n), n >= 1, into out (QZK_L4S_BOUND(n) - 4 bytes are enough); table: QZK_L4S_HSIZE words of LDS;
- * returns their size */
-QZ_DEV uint32_t qzk_l4s_block(const uint8_t *in, uint32_t n, uint8_t *out, uint32_t mm, uint32_t *table, int lane)
+/* what the parse hands its sequences to.  This one writes the LZ4s bytes; qzk_zstd.h has a second one, which keeps
+ * (literal length, match length, offset) records and the literal bytes for the zstd entropy stage.  An emitter E has
+ * qzk_l4s_emit(E &, lit, L, off, ml, mm, lane) - L literals and a match of ml >= mm bytes - and
+ * qzk_l4s_emit_tail(E &, lit, L, lane) - the L >= 1 literals a chunk ends with; both are called by the whole wave with
+ * wave-uniform arguments.  What the parse decides never depends on the emitter. */
+typedef struct { uint8_t *out; uint32_t op; } qzk_l4s_bytes;
+QZ_DEV void qzk_l4s_emit(qzk_l4s_bytes &e, const uint8_t *lit, uint32_t L, uint32_t off, uint32_t ml, uint32_t mm, int lane)
+{
+    e.op = qzk_l4s_seq(e.out, e.op, lit, L, off, ml, mm, lane);
+}
+QZ_DEV void qzk_l4s_emit_tail(qzk_l4s_bytes &e, const uint8_t *lit, uint32_t L, int lane) { e.op = qzk_l4s_tail(e.out, e.op, lit, L, lane); }
+
+/* the sequences of in[0..n), n >= 1, to the emitter; table: QZK_L4S_HSIZE words of LDS */
+template <typename E>
+QZ_DEV void qzk_l4s_parse(const uint8_t *in, uint32_t n, E &emit, uint32_t mm, uint32_t *table, int lane)
 {
     for (uint32_t i = (uint32_t)lane; i < QZK_L4S_HSIZE; i += 64) table[i] = 0;
     qz_lds_sync();
-    uint32_t cur = 0, anchor = 0, op = 0;
+    uint32_t cur = 0, anchor = 0;
     while (cur < n) {                                               /* cur grows by at least 64 a trip */
         const uint32_t p = cur + (uint32_t)lane;
         const bool valid = p + mm <= n;
@@ -172,15 +184,22 @@ QZ_DEV uint32_t qzk_l4s_block(const uint8_t *in, uint32_t n, uint8_t *out, uint3
              * offset only, so it is taken when the literals before it still fit the token (mini_match 3 only) */
             if (ml == 3 && pj - anchor >= 15) { m &= m - 1; continue; }
             if (ml >= QZK_L4S_LANECAP) ml += qzk_lz4_count(in + pj + ml, in + c + ml, n - (pj + ml), lane);
-            op = qzk_l4s_seq(out, op, in + anchor, pj - anchor, pj - c, ml, mm, lane);
+            qzk_l4s_emit(emit, in + anchor, pj - anchor, pj - c, ml, mm, lane);
             anchor = pj + ml;
             const uint32_t nx = (uint32_t)j + ml;
             m = nx >= 64 ? 0 : m & ~qz_below((int)nx);
         }
         cur = anchor > cur + 64 ? anchor : cur + 64;
     }
-    if (anchor < n) op = qzk_l4s_tail(out, op, in + anchor, n - anchor, lane);
-    return op;
+    if (anchor < n) qzk_l4s_emit_tail(emit, in + anchor, n - anchor, lane);
+}
+
+/* the sequences of in[0..n), n >= 1, as LZ4s bytes into out (QZK_L4S_BOUND(n) - 4 bytes are enough); returns their size */
+QZ_DEV uint32_t qzk_l4s_block(const uint8_t *in, uint32_t n, uint8_t *out, uint32_t mm, uint32_t *table, int lane)
+{
+    qzk_l4s_bytes e = { out, 0 };
+    qzk_l4s_parse(in, n, e, mm, table, lane);
+    return e.op;
 }
 
 /* K4s: persistent single-wave workgroups pull chunk numbers (as qzk_lz4c_pull_kernel); chunk b of the launch goes to slot b
