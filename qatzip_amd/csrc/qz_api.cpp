@@ -33,8 +33,7 @@
 #include "../../include/qatzip.h"
 #include "../../include/qzamd_device.h"
 #include "../../include/qzamd_zstd.h"
-
-enum { F_4B = 0, F_GZIP, F_GZIP_EXT, F_RAW, F_LZ4, F_LZ4S, F_ZLIB };   /* DataFormatInternal_T order, src/qatzip_internal.h:238-253 */
+#include "qz_frame.h"                   /* the F_* formats, bounds, the delivery rule, member framing, the crc folds */
 
 struct Params {
     QzHuffmanHdr_T huffman_hdr; QzDirection_T direction; int fmt; unsigned comp_lvl; unsigned char comp_algorithm;
@@ -437,31 +436,32 @@ static int reserve(Sess *s, size_t in_n, size_t out_n)
     return QZ_OK;
 }
 
-static void wr32(unsigned char *p, uint32_t v) { p[0] = (unsigned char)v; p[1] = (unsigned char)(v >> 8); p[2] = (unsigned char)(v >> 16); p[3] = (unsigned char)(v >> 24); }
-static uint32_t rd32(const unsigned char *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
 static uint32_t rd16(const unsigned char *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8; }
-
-static unsigned hdr_len(int fmt) { return fmt == F_GZIP ? 10 : fmt == F_GZIP_EXT ? 24 : fmt == F_ZLIB ? 2 : fmt == F_4B ? 4 : 0; }
-static unsigned ftr_len(int fmt) { return (fmt == F_GZIP || fmt == F_GZIP_EXT) ? 8 : fmt == F_ZLIB ? 4 : 0; }
-
-extern "C" uint32_t qzd_crc32_combine(uint32_t crc1, uint32_t crc2, uint64_t len2);   /* qzd_device.hip */
-static void wr32be(unsigned char *p, uint32_t v) { p[0] = (unsigned char)(v >> 24); p[1] = (unsigned char)(v >> 16); p[2] = (unsigned char)(v >> 8); p[3] = (unsigned char)v; }
-
-/* member header with the size fields still zero (src/qatzip_sw.c:61-75,158-171 and zlib's own gzip / zlib headers) */
-static void write_header(unsigned char *dest, int fmt, unsigned lvl)
-{
-    const unsigned char xfl = lvl == 9 ? 2 : lvl < 2 ? 4 : 0;       /* zlib's gzip XFL: 2 = best, 4 = fastest */
-    if (fmt == F_GZIP) { static const unsigned char h[10] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 4, 3}; memcpy(dest, h, 10); dest[8] = xfl; }
-    else if (fmt == F_GZIP_EXT) { static const unsigned char h[24] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 4, 255, 12, 0, 'Q', 'Z', 8, 0}; memcpy(dest, h, 24); dest[8] = xfl; }
-    else if (fmt == F_4B) wr32(dest, 0);
-    else if (fmt == F_ZLIB) {                                       /* CMF deflate/32K window; FLG = FLEVEL by level + FCHECK */
-        static const unsigned char flg[4] = {0x01, 0x5e, 0x9c, 0xda};
-        dest[0] = 0x78; dest[1] = flg[lvl < 2 ? 0 : lvl < 6 ? 1 : lvl == 6 ? 2 : 3];
-    }
-}
 
 /* ------------------------------------------------------------------ compress */
 static bool pinned_span(const void *p, size_t len);
+/* the end of every call that came somewhere: the lengths and the session's totals */
+static int deliver(QzSession_T *sess, unsigned int *src_len, unsigned int *dest_len, uint32_t used, uint64_t out, int rc)
+{
+    *src_len = used; *dest_len = (unsigned int)out;
+    sess->total_in += used; sess->total_out += out;
+    return rc;
+}
+/* ... of one whose items lie at d_out as they go to dest, lens[k] bytes each: the whole ones that fit, QZ_BUF_ERROR with
+ * progress otherwise (the hardware contract).  crc (an LZ4s call): the CRC-32 of the input consumed, folded in. */
+static int deliver_items(QzSession_T *sess, Sess *s, const std::vector<uint32_t> &lens, uint32_t n, uint32_t cap, unsigned int *src_len,
+                         unsigned char *dest, unsigned int *dest_len, unsigned long *crc)
+{
+    const QzFit f = qz_fit(0, 0, 0, lens.data(), (uint32_t)lens.size(), cap);
+    if (f.take == 0) return QZ_BUF_ERROR;
+    if (qzd_d2h(s->ctx, dest, s->d_out, f.bytes) != QZD_OK) return QZ_FAIL;
+    const QzDone d = qz_delivered(f.take, (uint32_t)lens.size(), n, s->p.hw_buff_sz);
+    uint32_t c = 0;
+    if (crc && qzd_crc32(s->ctx, s->d_in, d.used, &c) != QZD_OK) return QZ_FAIL;
+    if (crc) qz_crc_fold_lz4s(crc, c, d.used);
+    return deliver(sess, src_len, dest_len, d.used, f.bytes, d.rc);
+}
+
 static int compress_deflate(QzSession_T *sess, Sess *s, const unsigned char *src, unsigned int *src_len,
                             unsigned char *dest, unsigned int *dest_len, unsigned int last, unsigned long *crc)
 {
@@ -474,7 +474,7 @@ static int compress_deflate(QzSession_T *sess, Sess *s, const unsigned char *src
     *src_len = 0; *dest_len = 0;
     if (cap < hl) return QZ_BUF_ERROR;
     const uint32_t nchunks = n ? (n + hw - 1) / hw : 1;
-    const uint64_t worst = (uint64_t)n + (uint64_t)nchunks * (5ull * (hw / 32767 + 2) + 16) + 64;
+    const uint64_t worst = qz_deflate_bound(n, nchunks, hw);
     int rc = reserve(s, n, worst);
     if (rc) return rc;
     uint64_t produced = 0;
@@ -494,60 +494,33 @@ static int compress_deflate(QzSession_T *sess, Sess *s, const unsigned char *src
         s->adlers.resize(nchunks);
         if (qzd_adler32_chunks(s->ctx, s->d_in, n, hw, s->adlers.data()) != QZD_OK) return QZ_FAIL;
     }
-    /* how many whole chunks fit into dest (header now, trailer only with the final chunk)? */
-    uint32_t take = nchunks; uint64_t bytes = produced;
-    const unsigned fl = last ? ftr_len(fmt) : 0;
-    if (hl + produced + fl > cap) {
+    QzFit f = {nchunks, produced};
+    if (hl + produced + fl_all > cap) {
         if (qzd_chunk_lens(s->ctx, s->lens.data(), nchunks) != QZD_OK) return QZ_FAIL;
-        bytes = 0; take = 0;
-        while (take < nchunks && hl + bytes + s->lens[take] <= cap) bytes += s->lens[take++];
-        if (take == nchunks) take--, bytes -= s->lens[take];      /* the trailer is what does not fit */
-        if (take == 0) return QZ_BUF_ERROR;
+        f = qz_fit(hl, 0, fl_all, s->lens.data(), nchunks, cap);
+        if (f.take == 0) return QZ_BUF_ERROR;
     }
-    const bool complete = take == nchunks;
-    const uint32_t used = complete ? n : take * hw;
-    if (opening) {                                                  /* header, src/qatzip_sw.c:61-75,158-171 and zlib's own gzip header */
-        write_header(dest, fmt, lvl);
+    const QzDone d = qz_delivered(f.take, nchunks, n, hw);
+    if (opening) {
+        qz_member_open(dest, fmt, (int)lvl, false);
         s->open = true; s->run_sum = fmt == F_ZLIB ? 1u : 0u; s->st_in = 0; s->st_out = hl;
     }
-    if (bytes && !direct && qzd_d2h(s->ctx, dest + hl, s->d_out, bytes) != QZD_OK) return QZ_FAIL;
-    /* running CRC-32 of the stream (zlib's strm->adler for gzip) + the crc out-parameter of
-     * src/qatzip_sw.c:217-230, including its cumulative-fold behaviour on multi-chunk calls */
-    uint32_t done_in = 0;
-    for (uint32_t k = 0; k < take; k++) {
-        uint32_t cl = std::min<uint32_t>(hw, n - k * hw);
-        if (fmt == F_GZIP || fmt == F_GZIP_EXT) s->run_sum = qzd_crc32_combine(s->run_sum, s->crcs[k], cl);
-        else if (fmt == F_ZLIB) s->run_sum = qzd_adler32_combine(s->run_sum, s->adlers[k], cl);
-        done_in += cl;
-        if (crc) {
-            if (fmt == F_RAW) *crc = qzd_crc32_combine((uint32_t)*crc, s->crcs[k], cl);
-            else {
-                uint32_t adler = (fmt == F_4B) ? 1u : s->run_sum;
-                if (*crc == 0) *crc = adler; else *crc = qzd_crc32_combine((uint32_t)*crc, adler, done_in);
-            }
-        }
-    }
-    s->st_in += used; s->st_out += bytes;
-    uint32_t out_total = hl + (uint32_t)bytes;
-    if (complete && last) {
-        if (fmt == F_GZIP || fmt == F_GZIP_EXT) { wr32(dest + out_total, s->run_sum); wr32(dest + out_total + 4, (uint32_t)s->st_in); out_total += 8; s->st_out += 8; }
-        if (fmt == F_ZLIB) { wr32be(dest + out_total, s->run_sum); out_total += 4; s->st_out += 4; }
-        if (opening && fmt == F_GZIP_EXT) { wr32(dest + 16, (uint32_t)s->st_in); wr32(dest + 20, (uint32_t)(s->st_out - 24 - 8)); }
-        if (opening && fmt == F_4B) wr32(dest, (uint32_t)(s->st_out - 4));
+    if (f.bytes && !direct && qzd_d2h(s->ctx, dest + hl, s->d_out, f.bytes) != QZD_OK) return QZ_FAIL;
+    s->run_sum = qz_fold_chunks(crc, fmt, s->run_sum, s->crcs.data(), s->adlers.data(), f.take, n, hw);   /* zlib's strm->adler, and the crc out-parameter */
+    s->st_in += d.used; s->st_out += f.bytes;
+    uint32_t out_total = hl + (uint32_t)f.bytes;
+    if (d.rc == QZ_OK && last) {
+        const unsigned fl = qz_member_close(opening ? dest : NULL, dest + out_total, fmt, s->run_sum, (uint32_t)s->st_in, (uint32_t)f.bytes);
+        out_total += fl; s->st_out += fl;
         s->open = false;
     }
-    *src_len = used; *dest_len = out_total;
-    sess->total_in += used; sess->total_out += out_total;
-    return complete ? QZ_OK : QZ_BUF_ERROR;
+    return deliver(sess, src_len, dest_len, d.used, out_total, d.rc);
 }
 
 /* The HARDWARE path's framing (qzamd_set_hw_framing / QATZIP_AMD_HW_FRAMING=1): every hw_buff_sz chunk becomes a
- * complete member of its own - header, a deflate stream that ends with BFINAL, footer - the way doCompressOut retires a
- * chunk (src/qatzip.c:1691-1718: outputHeaderGen, payload, outputFooterGen).  GZIP_EXT: qzGzipHeaderGen
- * (src/qatzip_gzip.c:98-118: XFL 0, OS 255, both sizes in the 'QZ' extra field) + CRC-32 / ISIZE of the chunk; GZIP:
- * stdGzipHeaderGen (:120-136) + the same footer; 4B: the chunk's compressed length (qz4BHeaderGen :138-143); RAW has no
- * framing and keeps the software path's stream.  `last` plays no part (every call is closed), the crc out-parameter is the
- * CRC-32 of the data (crc32_combine over the chunks, src/qatzip.c:1711).  Interop: this is what streams from QAT boxes
+ * complete member of its own - header, a deflate stream that ends with BFINAL, footer (qz_hw_member) - the way doCompressOut
+ * retires a chunk (src/qatzip.c:1691-1718); RAW has no framing and keeps the software path's stream.  `last` plays no part
+ * (every call is closed), the crc out-parameter is the CRC-32 of the data.  Interop: this is what streams from QAT boxes
  * look like, and decompress_sized_members() reads thousands of such members in one launch. */
 static int compress_deflate_hw(QzSession_T *sess, Sess *s, const unsigned char *src, unsigned int *src_len,
                                unsigned char *dest, unsigned int *dest_len, unsigned long *crc)
@@ -558,10 +531,9 @@ static int compress_deflate_hw(QzSession_T *sess, Sess *s, const unsigned char *
     if (s->p.comp_lvl < 1 || s->p.comp_lvl > 9) return QZ_NOT_SUPPORTED;
     if (n == 0) return QZ_OK;                                       /* (not reached: calls below input_sz_thrshold take the software path) */
     const uint32_t nchunks = (n + hw - 1) / hw;
-    const unsigned hl = fmt == F_GZIP_EXT ? 24 : fmt == F_GZIP ? 10 : 4, fl = fmt == F_4B ? 0 : 8;
+    const unsigned hl = hdr_len(fmt), fl = ftr_len(fmt);
     const uint64_t in_bytes = (uint64_t)nchunks * hw;
-    const uint64_t worst = in_bytes + (uint64_t)nchunks * (5ull * (hw / 32767 + 2) + 16) + 64;
-    int rc = reserve(s, in_bytes, worst);
+    int rc = reserve(s, in_bytes, qz_deflate_bound(in_bytes, nchunks, hw));
     if (rc) return rc;
     if (qzd_h2d(s->ctx, s->d_in, src, n) != QZD_OK) return QZ_FAIL;
     std::vector<uint32_t> cdesc(nchunks), lens(nchunks), crcs(nchunks);
@@ -572,31 +544,20 @@ static int compress_deflate_hw(QzSession_T *sess, Sess *s, const unsigned char *
         logmsg(LOG_ERROR, "GPU deflate failed: %s\n", qzd_last_error(s->ctx));
         return QZ_FAIL;
     }
-    /* whole members that fit */
-    uint32_t take = 0; uint64_t bytes = 0, body = 0;
-    while (take < nchunks && bytes + hl + lens[take] + fl <= cap) { bytes += hl + lens[take] + fl; body += lens[take]; take++; }
-    if (take == 0) return QZ_BUF_ERROR;
+    const QzFit f = qz_fit(0, hl + fl, 0, lens.data(), nchunks, cap);  /* whole members that fit */
+    if (f.take == 0) return QZ_BUF_ERROR;
+    const uint64_t body = f.bytes - (uint64_t)f.take * (hl + fl);
     try { s->hw_stage.resize(body); } catch (const std::bad_alloc &) { return QZ_NOSW_LOW_MEM; }
     if (body && qzd_d2h(s->ctx, s->hw_stage.data(), s->d_out, body) != QZD_OK) return QZ_FAIL;
     unsigned char *o = dest; const unsigned char *b = s->hw_stage.data();
-    for (uint32_t k = 0; k < take; k++) {
-        const uint32_t cl = cdesc[k] & 0x7fffffffu, zl = lens[k];
-        if (fmt == F_GZIP_EXT) {
-            static const unsigned char h[16] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 255, 12, 0, 'Q', 'Z', 8, 0};
-            memcpy(o, h, 16); wr32(o + 16, cl); wr32(o + 20, zl);
-        } else if (fmt == F_GZIP) {
-            static const unsigned char h[10] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 0, 255};
-            memcpy(o, h, 10);
-        } else wr32(o, zl);
-        memcpy(o + hl, b, zl);
-        if (fl) { wr32(o + hl + zl, crcs[k]); wr32(o + hl + zl + 4, cl); }
-        if (crc) *crc = (*crc == 0 && k == 0) ? crcs[k] : qzd_crc32_combine((uint32_t)*crc, crcs[k], cl);
-        o += hl + zl + fl; b += zl;
+    for (uint32_t k = 0; k < f.take; k++) {
+        const uint32_t cl = cdesc[k] & 0x7fffffffu;
+        o += qz_hw_member(o, fmt, b, lens[k], cl, crcs[k]);
+        b += lens[k];
+        if (crc) qz_crc_fold_hw(crc, k, crcs[k], cl);
     }
-    const uint32_t used = take == nchunks ? n : take * hw;
-    *src_len = used; *dest_len = (unsigned int)bytes;
-    sess->total_in += used; sess->total_out += bytes;
-    return take == nchunks ? QZ_OK : QZ_BUF_ERROR;
+    const QzDone d = qz_delivered(f.take, nchunks, n, hw);
+    return deliver(sess, src_len, dest_len, d.used, f.bytes, d.rc);
 }
 
 /* An LZ4 session in the HARDWARE path's framing (qzamd_set_hw_framing): every hw_buff_sz chunk is a frame of its own
@@ -604,7 +565,7 @@ static int compress_deflate_hw(QzSession_T *sess, Sess *s, const unsigned char *
  * consumed, header checksum - and in front of qzLZ4FooterGen's end mark + XXH32 of the chunk (src/qatzip_lz4.c:104-143;
  * retired chunk by chunk, src/qatzip.c:1691-1718).  A chunk of at most 64 KB is one block; a larger hw_buff_sz gives the
  * frame several 64 KB blocks that may reach back into each other, which is what the linked-block kernel writes (its
- * header is this very one).  Whole frames that fit, QZ_BUF_ERROR with progress otherwise (the hardware contract). */
+ * header is this very one). */
 static int compress_lz4_hw(QzSession_T *sess, Sess *s, const unsigned char *src, unsigned int *src_len,
                            unsigned char *dest, unsigned int *dest_len)
 {
@@ -622,20 +583,12 @@ static int compress_lz4_hw(QzSession_T *sess, Sess *s, const unsigned char *src,
     /* one launch for all chunks, whatever hw_buff_sz: one-block frames up to 64 KB, linked blocks above (a wave per chunk) */
     if (lvl >= 3) { if (qzd_lz4hc_compress_frames_hw(s->ctx, s->d_in, n, hw, (int)lvl, s->d_out, s->out_cap, &produced, lens.data()) != QZD_OK) return QZ_FAIL; }
     else if (qzd_lz4_compress_frames_hw(s->ctx, s->d_in, n, hw, s->d_out, s->out_cap, &produced, lens.data()) != QZD_OK) return QZ_FAIL;
-    uint32_t take = 0; uint64_t bytes = 0;
-    while (take < nchunks && bytes + lens[take] <= cap) bytes += lens[take++];
-    if (take == 0) return QZ_BUF_ERROR;
-    if (qzd_d2h(s->ctx, dest, s->d_out, bytes) != QZD_OK) return QZ_FAIL;
-    const uint32_t used = take == nchunks ? n : take * hw;
-    *src_len = used; *dest_len = (unsigned int)bytes;
-    sess->total_in += used; sess->total_out += bytes;
-    return take == nchunks ? QZ_OK : QZ_BUF_ERROR;
+    return deliver_items(sess, s, lens, n, cap, src_len, dest, dest_len, NULL);
 }
 
 /* LZ4s sessions (src/qatzip.c:1304-1337; block header src/qatzip_lz4.c:219-231, no footer): every hw_buff_sz chunk of the
  * call is one block - u32le size, LZ77 sequences ("LZ4s sessions") - for the session's post-processing
- * callback.  Whole blocks that fit, QZ_BUF_ERROR with progress otherwise, as compress_lz4_hw.  Every call goes to the GPU:
- * there is no software LZ4s compressor to send a small one to. */
+ * callback.  Every call goes to the GPU: there is no software LZ4s compressor to send a small one to. */
 static int compress_lz4s(QzSession_T *sess, Sess *s, const unsigned char *src, unsigned int *src_len,
                          unsigned char *dest, unsigned int *dest_len, unsigned long *crc)
 {
@@ -655,19 +608,7 @@ static int compress_lz4s(QzSession_T *sess, Sess *s, const unsigned char *src, u
         logmsg(LOG_ERROR, "GPU %s failed: %s\n", s->p.zstd ? "zstd" : "LZ4s", qzd_last_error(s->ctx));
         return QZ_FAIL;
     }
-    uint32_t take = 0; uint64_t bytes = 0;
-    while (take < nchunks && bytes + lens[take] <= cap) bytes += lens[take++];
-    if (take == 0) return QZ_BUF_ERROR;
-    if (qzd_d2h(s->ctx, dest, s->d_out, bytes) != QZD_OK) return QZ_FAIL;
-    const uint32_t used = take == nchunks ? n : take * hw;
-    if (crc) {
-        uint32_t c = 0;
-        if (qzd_crc32(s->ctx, s->d_in, used, &c) != QZD_OK) return QZ_FAIL;
-        *crc = qzd_crc32_combine((uint32_t)*crc, c, used);
-    }
-    *src_len = used; *dest_len = (unsigned int)bytes;
-    sess->total_in += used; sess->total_out += bytes;              /* LZ4s bytes, before post-processing (src/qatzip.c:2064-2065) */
-    return take == nchunks ? QZ_OK : QZ_BUF_ERROR;
+    return deliver_items(sess, s, lens, n, cap, src_len, dest, dest_len, crc);     /* LZ4s bytes, before post-processing (src/qatzip.c:2064-2065) */
 }
 
 /* LZ4 sessions: one frame per call, `last` ignored (src/qatzip_sw.c:443-471) */
@@ -688,7 +629,7 @@ static int compress_lz4(QzSession_T *sess, Sess *s, const unsigned char *src, un
     if (lvl >= 9) return QZ_NOT_SUPPORTED;
     const bool linked = n > 65536 && n <= 0x7fff0000u;
     const uint64_t nfr = n ? ((uint64_t)n + 65535) >> 16 : 1;
-    const uint64_t bound = linked ? 19 + 4 * nfr + (uint64_t)n + 8 : nfr * (19 + 4 + 8) + (uint64_t)n;   /* LZ4F_compressFrameBound */
+    const uint64_t bound = linked ? qzd_lz4_linked_bound(n) : nfr * (19 + 4 + 8) + (uint64_t)n;   /* LZ4F_compressFrameBound */
     if (cap < bound) return QZ_FAIL;                               /* LZ4F_ERROR_dstMaxSize_tooSmall => QZ_FAIL */
     int rc = reserve(s, n, bound + 64);
     if (rc) return rc;
@@ -701,9 +642,7 @@ static int compress_lz4(QzSession_T *sess, Sess *s, const unsigned char *src, un
     else if (linked) { if (qzd_lz4_compress_linked(s->ctx, s->d_in, n, s->d_out, s->out_cap, &produced) != QZD_OK) return QZ_FAIL; }
     else if (qzd_lz4_compress_frames(s->ctx, s->d_in, n, 65536, s->d_out, s->out_cap, &produced, NULL) != QZD_OK) return QZ_FAIL;
     if (qzd_d2h(s->ctx, dest, s->d_out, produced) != QZD_OK) return QZ_FAIL;
-    *src_len = n; *dest_len = (unsigned int)produced;
-    sess->total_in += n; sess->total_out += produced;
-    return QZ_OK;
+    return deliver(sess, src_len, dest_len, n, produced, QZ_OK);
 }
 
 /* walk one LZ4 frame on the host: total frame length and (if present) content size; <0 on malformed input */
@@ -765,9 +704,7 @@ static int decompress_lz4(QzSession_T *sess, Sess *s, const unsigned char *src, 
     }
     if (produced && qzd_d2h(s->ctx, dest, s->d_out, produced) != QZD_OK) return QZ_FAIL;
     s->out_resident = true;
-    *src_len = ti; *dest_len = (unsigned int)produced;
-    sess->total_in += ti; sess->total_out += produced;
-    return (ti < n && to >= cap) ? QZ_OK : QZ_OK;
+    return deliver(sess, src_len, dest_len, ti, produced, QZ_OK);
 }
 
 /* Small synchronous calls from many threads share launches too (below: sync_via_queue) */
@@ -943,9 +880,7 @@ static int decompress_deflate(QzSession_T *sess, Sess *s, const unsigned char *s
         s->hold_pos += k;
         const bool last_piece = s->hold_pos == s->hold_len && n >= 1;     /* the held-back byte has to be there to be consumed */
         if (last_piece) { qzd_dev_free(s->ctx, s->d_hold); s->d_hold = NULL; s->hold_len = s->hold_pos = 0; s->end_of_stream = 1; }
-        *src_len = last_piece ? 1 : 0; *dest_len = k;
-        sess->total_in += *src_len; sess->total_out += k;
-        return QZ_OK;
+        return deliver(sess, src_len, dest_len, last_piece ? 1 : 0, k, QZ_OK);
     }
     int rc = reserve(s, n, cap);
     if (rc) return rc;
@@ -1027,9 +962,7 @@ static int decompress_deflate(QzSession_T *sess, Sess *s, const unsigned char *s
                 *crc = *crc == 0 ? c : qzd_crc32_combine((uint32_t)*crc, c, k);
             }
             s->hold_len = ol; s->hold_pos = k;
-            *src_len = pos - 1; *dest_len = k;
-            sess->total_in += pos - 1; sess->total_out += k;
-            return QZ_OK;
+            return deliver(sess, src_len, dest_len, pos - 1, k, QZ_OK);
         }
         if (crc) *crc = (to == 0 && *crc == 0) ? c32 : qzd_crc32_combine((uint32_t)*crc, c32, ol);
         ti = pos; to += (uint32_t)ol;
@@ -1043,10 +976,8 @@ static int decompress_deflate(QzSession_T *sess, Sess *s, const unsigned char *s
     if (ret == QZ_DATA_ERROR && ti > 0) ret = QZ_OK;
     if (ret != QZ_OK && !(ret == QZ_BUF_ERROR && to > 0)) { *src_len = 0; *dest_len = 0; return ret; }
     if (to && !(all_sent && sent_bytes == to) && qzd_d2h(s->ctx, dest, s->d_out, to) != QZD_OK) return QZ_FAIL;
-    *src_len = ti; *dest_len = to;
-    sess->total_in += ti; sess->total_out += to;
     s->out_resident = true;
-    return ret;
+    return deliver(sess, src_len, dest_len, ti, to, ret);
 }
 
 static int decompress_direct(QzSession_T *sess, const unsigned char *src, unsigned int *src_len, unsigned char *dest,
@@ -1368,7 +1299,7 @@ static bool compress_batch(const std::vector<AsyncReq> &run, const std::vector<S
     }
     const uint32_t nslots = (uint32_t)cdesc.size();
     const uint64_t in_bytes = (uint64_t)nslots * hw;
-    const uint64_t worst = in_bytes + (uint64_t)nslots * (5ull * (hw / 32767 + 2) + 16) + 64;
+    const uint64_t worst = qz_deflate_bound(in_bytes, nslots, hw);
     if (in_bytes > AQ_BATCH_MAX_BYTES + AQ_BATCH_MAX_REQ + hw || reserve(s0, in_bytes, worst) != QZ_OK) return false;
     /* slot-aligned copy of every request's input in the queue's pinned staging buffer (allocated once, reused, never
      * zeroed: the gaps between requests are not read - cdesc carries each slot's length), then ONE copy to the device */
@@ -1398,25 +1329,10 @@ static bool compress_batch(const std::vector<AsyncReq> &run, const std::vector<S
             continue;
         }
         unsigned long *crc = req_crc(run[i]);
-        write_header(dest, fmt, lvl);
+        qz_member_open(dest, fmt, (int)lvl, false);
         memcpy(dest + hl, stage + bpos, body);
-        uint32_t sum = 0, done = 0;
-        for (uint32_t k = 0; k < nch; k++) {                    /* same folds as compress_deflate */
-            const uint32_t cl = cdesc[k0 + k] & 0x7fffffffu;
-            if (fmt == F_GZIP || fmt == F_GZIP_EXT) sum = qzd_crc32_combine(sum, crcs[k0 + k], cl);
-            done += cl;
-            if (crc) {
-                if (fmt == F_RAW) *crc = qzd_crc32_combine((uint32_t)*crc, crcs[k0 + k], cl);
-                else {
-                    const uint32_t adler = fmt == F_4B ? 1u : sum;
-                    if (*crc == 0) *crc = adler; else *crc = qzd_crc32_combine((uint32_t)*crc, adler, done);
-                }
-            }
-        }
-        uint32_t total = hl + (uint32_t)body;
-        if (fmt == F_GZIP || fmt == F_GZIP_EXT) { wr32(dest + total, sum); wr32(dest + total + 4, n); total += 8; }
-        if (fmt == F_GZIP_EXT) { wr32(dest + 16, n); wr32(dest + 20, (uint32_t)body); }
-        if (fmt == F_4B) wr32(dest, (uint32_t)body);
+        const uint32_t sum = qz_fold_chunks(crc, fmt, 0, crcs.data() + k0, NULL, nch, n, hw);
+        const uint32_t total = hl + (uint32_t)body + qz_member_close(dest, dest + hl + body, fmt, sum, n, (uint32_t)body);
         r->dest_len = total; r->ext_rc = 0; r->status = QZ_OK;  /* src_len: all of it */
         run[i].sess->total_in += n; run[i].sess->total_out += total; run[i].sess->thd_sess_stat = QZ_OK;
     }
@@ -1872,8 +1788,7 @@ extern "C" int qzCompressWithMetadataExt(QzSession_T *sess, const unsigned char 
         if (n == 0) { *dest_len = 0; return QZ_OK; }
         const uint32_t nb = (uint32_t)(((uint64_t)n + B - 1) / B);
         if (nb > h->nblocks) { rc = QZ_METADATA_OVERFLOW; goto fail; }
-        const uint64_t worst = (uint64_t)n + (uint64_t)nb * (5ull * (B / 32767 + 2) + 16) + 64;
-        rc = reserve(s, (uint64_t)nb * B, worst);
+        rc = reserve(s, (uint64_t)nb * B, qz_deflate_bound(n, nb, B));
         if (rc) goto fail;
         if (qzd_h2d(s->ctx, s->d_in, src, n) != QZD_OK) { rc = QZ_FAIL; goto fail; }
         std::vector<qzd_blockrec> recs(nb);
@@ -1896,12 +1811,9 @@ extern "C" int qzCompressWithMetadataExt(QzSession_T *sess, const unsigned char 
             r.in_crc32 = d.in_crc32; r.out_crc32 = d.out_crc32; r.in_crc64 = d.in_crc64; r.out_crc64 = d.out_crc64;
             r.check = meta_check(r);
         }
-        const uint32_t used = take == nb ? n : take * B;
-        *src_len = used; *dest_len = (unsigned int)bytes;
-        sess->total_in += used; sess->total_out += bytes;
-        rc = take == nb ? QZ_OK : QZ_BUF_ERROR;
-        sess->thd_sess_stat = rc;
-        return rc;
+        const QzDone d = qz_delivered(take, nb, n, B);
+        sess->thd_sess_stat = d.rc;
+        return deliver(sess, src_len, dest_len, d.used, bytes, d.rc);
     }
 fail:
     if (src_len) *src_len = 0;
@@ -1951,10 +1863,8 @@ extern "C" int qzDecompressWithMetadataExt(QzSession_T *sess, const unsigned cha
         if (r != QZD_OK) { logmsg(LOG_ERROR, "GPU block decompress failed: %s\n", qzd_last_error(s->ctx)); rc = QZ_FAIL; goto fail; }
         if (produced > cap) { rc = QZ_BUF_ERROR; goto fail; }
         if (produced && qzd_d2h(s->ctx, dest, s->d_out, produced) != QZD_OK) { rc = QZ_FAIL; goto fail; }
-        *src_len = (unsigned int)end; *dest_len = (unsigned int)produced;
-        sess->total_in += end; sess->total_out += produced;
         sess->thd_sess_stat = QZ_OK;
-        return QZ_OK;
+        return deliver(sess, src_len, dest_len, (uint32_t)end, produced, QZ_OK);
     }
 fail:
     if (src_len) *src_len = 0;

@@ -28,6 +28,7 @@
 #include "qzd_internal.h"
 #include "qzk_deflate_huff.h"
 #include "qzk_checksum.h"
+#include "qzd_slot_host.h"
 
 /* per call: chunk offsets (8 B each) and, behind them, what a launch that moves the stream itself needs (qzk_outp): the
  * front word and one published length per chunk */
@@ -515,6 +516,31 @@ static int finish_sync_call(qzd_ctx *c, hipStream_t st, uint64_t *h_out_len)
     HIPCHK(c, hipGetLastError());
     if (*c->h_overflow) { snprintf(c->err, sizeof(c->err), "destination too small"); return QZD_ERR_DSTCAP; }
     *h_out_len = *c->h_running;
+    return QZD_OK;
+}
+
+/* A call of the wave-per-chunk compressors (LZ4, LZ4s and zstd frames): `items` chunks in rounds of `batch` (qzd_slot_batch),
+ * each written to a slot of `stride` bytes by launch_round(b, bn, slots) - the bn chunks from chunk b, lengths to c->d_len + b,
+ * on c->st[0] - and gathered behind it.  before_wait() enqueues what the caller reads once the stream is idle. */
+static int no_hook(void) { return QZD_OK; }
+template <class Round, class BeforeWait = int (*)(void)>
+static int slot_rounds(qzd_ctx *c, uint32_t items, uint32_t stride, uint32_t batch, uint8_t *d_dst, uint64_t dst_cap,
+                       uint64_t *h_out_len, uint32_t *h_item_len, Round launch_round, BeforeWait before_wait = no_hook)
+{
+    QZD_TRY(reserve_call_arrays(c, items));
+    QZD_TRY(grow_dev(c, (void **)&c->lz4_slots, &c->slot_cap, (size_t)batch * stride));
+    hipStream_t st = c->st[0];
+    QZD_TRY(call_begin(c, st, items, c->nbatches));    /* (the stage events of qzd_last_timing stay the last deflate call's) */
+    for (uint32_t b = 0; b < items; b += batch) {
+        const uint32_t bn = items - b < batch ? items - b : batch;
+        QZD_TRY(launch_round(b, bn, c->lz4_slots));
+        launch_scan_gather(c, st, c->lz4_slots, stride, b, bn, d_dst, dst_cap);
+    }
+    HIPCHK(c, hipEventRecord(c->ev_end, st));
+    QZD_TRY(publish_totals(c, st));
+    QZD_TRY(before_wait());
+    QZD_TRY(finish_sync_call(c, st, h_out_len));
+    if (h_item_len) HIPCHK(c, hipMemcpy(h_item_len, c->d_len, (size_t)items * 4, hipMemcpyDeviceToHost));
     return QZD_OK;
 }
 
@@ -1070,16 +1096,6 @@ extern "C" int qzd_last_timing(qzd_ctx *c, float ms[4])
 /* every frame_sz bytes of d_src become one LZ4 frame (what one qzCompress call of an LZ4 session emits for
  * src_len <= 64 KB, src/qatzip_sw.c:443-471); frames are written back to back to d_dst */
 static int lz4_compress_frames_impl(qzd_ctx *c, const uint8_t *d_src, uint64_t n, uint32_t frame_sz,
-                                    uint8_t *d_dst, uint64_t dst_cap, uint64_t *h_out_len, uint32_t *h_frame_len, uint32_t hw_hdr);
-extern "C" int qzd_lz4_compress_frames(qzd_ctx *c, const uint8_t *d_src, uint64_t n, uint32_t frame_sz,
-                                       uint8_t *d_dst, uint64_t dst_cap, uint64_t *h_out_len, uint32_t *h_frame_len)
-{ return lz4_compress_frames_impl(c, d_src, n, frame_sz, d_dst, dst_cap, h_out_len, h_frame_len, 0); }
-/* the same frames behind the header of the reference's hardware path (FLG 0x4C, content size = the chunk's bytes,
- * src/qatzip_lz4.c:104-132): what a QAT box writes per hw_buff_sz chunk of an LZ4 session */
-extern "C" int qzd_lz4_compress_frames_hw(qzd_ctx *c, const uint8_t *d_src, uint64_t n, uint32_t frame_sz,
-                                          uint8_t *d_dst, uint64_t dst_cap, uint64_t *h_out_len, uint32_t *h_frame_len)
-{ return lz4_compress_frames_impl(c, d_src, n, frame_sz, d_dst, dst_cap, h_out_len, h_frame_len, 1); }
-static int lz4_compress_frames_impl(qzd_ctx *c, const uint8_t *d_src, uint64_t n, uint32_t frame_sz,
                                     uint8_t *d_dst, uint64_t dst_cap, uint64_t *h_out_len, uint32_t *h_frame_len, uint32_t hw_hdr)
 {
     if (!c || !d_dst || (n && !d_src) || !h_out_len) return QZD_ERR_PARAM;
@@ -1090,15 +1106,8 @@ static int lz4_compress_frames_impl(qzd_ctx *c, const uint8_t *d_src, uint64_t n
     hipSetDevice(c->device);
     const uint32_t nfr = n ? (uint32_t)((n + frame_sz - 1) / frame_sz) : 1;
     const uint32_t stride = (frame_sz + 15 + 4 * ((frame_sz + 65535) >> 16) + 8 + 64 + 15) & ~15u;
-    QZD_TRY(reserve_call_arrays(c, nfr));
-    uint32_t batch = nfr < 16384u ? nfr : 16384u;
-    if (linked && (uint64_t)batch * stride > (1ull << 30)) batch = std::max<uint32_t>(1u, (uint32_t)((1ull << 30) / stride));   /* slots of a gigabyte at most */
-    QZD_TRY(grow_dev(c, (void **)&c->lz4_slots, &c->slot_cap, (size_t)batch * stride));
-    uint8_t *const slots = c->lz4_slots;
     hipStream_t st = c->st[0];
-    QZD_TRY(call_begin(c, st, nfr, c->nbatches));      /* (the stage events of qzd_last_timing stay the last deflate call's) */
-    for (uint32_t b = 0; b < nfr; b += batch) {
-        const uint32_t bn = nfr - b < batch ? nfr - b : batch;
+    return slot_rounds(c, nfr, stride, qzd_slot_batch(nfr, stride, qzd_lz4_slot_budget(frame_sz)), d_dst, dst_cap, h_out_len, h_frame_len, [&](uint32_t b, uint32_t bn, uint8_t *slots) -> int {
         const uint64_t boff = (uint64_t)b * frame_sz;
         /* many frames: persistent waves with their hash tables in device memory, as many per CU as it has wave slots
          * (QATZIP_AMD_LZ4_WPC=<waves per CU>, 0 = the one-launch-per-frame kernel with the table in LDS) */
@@ -1135,14 +1144,17 @@ static int lz4_compress_frames_impl(qzd_ctx *c, const uint8_t *d_src, uint64_t n
             }
         } else
             hipLaunchKernelGGL(qzk_lz4c_kernel, dim3(bn), dim3(64), 0, st, d_src + boff, n - boff, frame_sz, bn, slots, stride, c->d_len + b, hw_hdr);
-        launch_scan_gather(c, st, slots, stride, b, bn, d_dst, dst_cap);
-    }
-    HIPCHK(c, hipEventRecord(c->ev_end, st));
-    QZD_TRY(publish_totals(c, st));
-    QZD_TRY(finish_sync_call(c, st, h_out_len));
-    if (h_frame_len) HIPCHK(c, hipMemcpy(h_frame_len, c->d_len, (size_t)nfr * 4, hipMemcpyDeviceToHost));
-    return QZD_OK;
+        return QZD_OK;
+    });
 }
+extern "C" int qzd_lz4_compress_frames(qzd_ctx *c, const uint8_t *d_src, uint64_t n, uint32_t frame_sz,
+                                       uint8_t *d_dst, uint64_t dst_cap, uint64_t *h_out_len, uint32_t *h_frame_len)
+{ return lz4_compress_frames_impl(c, d_src, n, frame_sz, d_dst, dst_cap, h_out_len, h_frame_len, 0); }
+/* the same frames behind the header of the reference's hardware path (FLG 0x4C, content size = the chunk's bytes,
+ * src/qatzip_lz4.c:104-132): what a QAT box writes per hw_buff_sz chunk of an LZ4 session */
+extern "C" int qzd_lz4_compress_frames_hw(qzd_ctx *c, const uint8_t *d_src, uint64_t n, uint32_t frame_sz,
+                                          uint8_t *d_dst, uint64_t dst_cap, uint64_t *h_out_len, uint32_t *h_frame_len)
+{ return lz4_compress_frames_impl(c, d_src, n, frame_sz, d_dst, dst_cap, h_out_len, h_frame_len, 1); }
 
 /* one call above 64 KB as the ONE frame with linked blocks that LZ4F_compressFrame writes for it (one wave, serial) */
 extern "C" int qzd_lz4_compress_linked(qzd_ctx *c, const uint8_t *d_src, uint64_t n, uint8_t *d_dst, uint64_t dst_cap,
@@ -1150,8 +1162,7 @@ extern "C" int qzd_lz4_compress_linked(qzd_ctx *c, const uint8_t *d_src, uint64_
 {
     if (!c || !d_src || !d_dst || !h_out_len) return QZD_ERR_PARAM;
     if (n <= QZK_LZ4_MAXBLK || n > 0x7fff0000ull) { snprintf(c->err, sizeof(c->err), "linked LZ4 frames: 64 KB < n <= 0x7fff0000"); return QZD_ERR_UNSUPPORTED; }
-    const uint64_t bound = 19 + 4 * ((n + 65535) >> 16) + n + 8;
-    if (dst_cap < bound) { snprintf(c->err, sizeof(c->err), "destination too small"); return QZD_ERR_DSTCAP; }
+    if (dst_cap < qzd_lz4_linked_bound(n)) { snprintf(c->err, sizeof(c->err), "destination too small"); return QZD_ERR_DSTCAP; }
     hipSetDevice(c->device);
     hipStream_t st = c->st[0];
     HIPCHK(c, hipEventRecord(c->ev_begin, st));
@@ -1245,8 +1256,7 @@ extern "C" int qzd_lz4hc_compress_linked(qzd_ctx *c, const uint8_t *d_src, uint6
 {
     if (!c || !d_src || !d_dst || !h_out_len) return QZD_ERR_PARAM;
     if (n <= QZK_LZ4_MAXBLK || n > 0x7fff0000ull) { snprintf(c->err, sizeof(c->err), "linked LZ4 frames: 64 KB < n <= 0x7fff0000"); return QZD_ERR_UNSUPPORTED; }
-    const uint64_t bound = 19 + 4 * ((n + 65535) >> 16) + n + 8;
-    if (dst_cap < bound) { snprintf(c->err, sizeof(c->err), "destination too small"); return QZD_ERR_DSTCAP; }
+    if (dst_cap < qzd_lz4_linked_bound(n)) { snprintf(c->err, sizeof(c->err), "destination too small"); return QZD_ERR_DSTCAP; }
     return lz4hc_impl(c, d_src, n, (uint32_t)n, level, 0, d_dst, dst_cap, h_out_len, NULL);
 }
 
@@ -1281,28 +1291,16 @@ extern "C" int qzd_lz4s_compress_blocks(qzd_ctx *c, const uint8_t *d_src, uint64
     hipSetDevice(c->device);
     const uint32_t nb = (uint32_t)((n + block_sz - 1) / block_sz);
     const uint32_t stride = (QZK_L4S_BOUND(block_sz) + 15) & ~15u;
-    QZD_TRY(reserve_call_arrays(c, nb));
-    uint32_t batch = nb < 16384u ? nb : 16384u;
-    if ((uint64_t)batch * stride > (1ull << 30)) batch = (uint32_t)((1ull << 30) / stride);       /* slots of a gigabyte at most */
-    QZD_TRY(grow_dev(c, (void **)&c->lz4_slots, &c->slot_cap, (size_t)batch * stride));
-    uint8_t *const slots = c->lz4_slots;
     hipStream_t st = c->st[0];
     const uint32_t cus = c->cus ? c->cus : 256u;
-    QZD_TRY(call_begin(c, st, nb, c->nbatches));
-    for (uint32_t b = 0; b < nb; b += batch) {
-        const uint32_t bn = nb - b < batch ? nb - b : batch;
+    return slot_rounds(c, nb, stride, qzd_slot_batch(nb, stride, QZD_SLOT_GIGABYTE), d_dst, dst_cap, h_out_len, h_block_len, [&](uint32_t b, uint32_t bn, uint8_t *slots) -> int {
         const uint64_t boff = (uint64_t)b * block_sz;
         /* persistent waves, as many as the device holds at once, pull the round's blocks from the stream's counter */
         HIPCHK(c, hipMemsetAsync(c->k1_counter, 0, 4, st));
         hipLaunchKernelGGL(qzk_lz4s_pull_kernel, dim3(std::min<uint32_t>(bn, QZD_L4S_WPC * cus)), dim3(64), 0, st, d_src + boff, n - boff,
                            block_sz, bn, slots, stride, c->d_len + b, mini_match, c->k1_counter);
-        launch_scan_gather(c, st, slots, stride, b, bn, d_dst, dst_cap);
-    }
-    HIPCHK(c, hipEventRecord(c->ev_end, st));
-    QZD_TRY(publish_totals(c, st));
-    QZD_TRY(finish_sync_call(c, st, h_out_len));
-    if (h_block_len) HIPCHK(c, hipMemcpy(h_block_len, c->d_len, (size_t)nb * 4, hipMemcpyDeviceToHost));
-    return QZD_OK;
+        return QZD_OK;
+    });
 }
 
 /* ------------------------------------------------------------------ zstd frames (Kz) */
@@ -1329,30 +1327,18 @@ extern "C" int qzd_zstd_compress_frames(qzd_ctx *c, const uint8_t *d_src, uint64
     hipSetDevice(c->device);
     const uint32_t nb = (uint32_t)((n + block_sz - 1) / block_sz);
     const uint32_t stride = qzd_zs_stride(block_sz);
-    QZD_TRY(reserve_call_arrays(c, nb));
-    uint32_t batch = nb < 16384u ? nb : 16384u;
-    if ((uint64_t)batch * stride > (1ull << 30)) batch = (uint32_t)((1ull << 30) / stride);       /* slots of a gigabyte at most */
-    QZD_TRY(grow_dev(c, (void **)&c->lz4_slots, &c->slot_cap, (size_t)batch * stride));
     /* records and literals per WAVE, not per chunk: a wave codes the chunk it parsed before it pulls the next */
     const uint32_t cus = c->cus ? c->cus : 256u;
-    const uint32_t waves = std::min<uint32_t>(batch, QZD_ZS_WPC * cus);
+    const uint32_t batch = qzd_slot_batch(nb, stride, QZD_SLOT_GIGABYTE), waves = std::min<uint32_t>(batch, QZD_ZS_WPC * cus);
     QZD_TRY(grow_dev(c, (void **)&c->d_lane, &c->lane_cap, (size_t)waves * QZK_ZS_WAVEB(block_sz)));
-    uint8_t *const slots = c->lz4_slots;
     hipStream_t st = c->st[0];
-    QZD_TRY(call_begin(c, st, nb, c->nbatches));
-    for (uint32_t b = 0; b < nb; b += batch) {
-        const uint32_t bn = nb - b < batch ? nb - b : batch;
+    return slot_rounds(c, nb, stride, batch, d_dst, dst_cap, h_out_len, h_frame_len, [&](uint32_t b, uint32_t bn, uint8_t *slots) -> int {
         const uint64_t boff = (uint64_t)b * block_sz;
         HIPCHK(c, hipMemsetAsync(c->k1_counter, 0, 4, st));
         hipLaunchKernelGGL(qzk_zstd_pull_kernel, dim3(std::min<uint32_t>(bn, waves)), dim3(64), 0, st, d_src + boff, n - boff,
                            block_sz, bn, slots, stride, c->d_len + b, mini_match, c->k1_counter, c->d_lane);
-        launch_scan_gather(c, st, slots, stride, b, bn, d_dst, dst_cap);
-    }
-    HIPCHK(c, hipEventRecord(c->ev_end, st));
-    QZD_TRY(publish_totals(c, st));
-    QZD_TRY(finish_sync_call(c, st, h_out_len));
-    if (h_frame_len) HIPCHK(c, hipMemcpy(h_frame_len, c->d_len, (size_t)nb * 4, hipMemcpyDeviceToHost));
-    return QZD_OK;
+        return QZD_OK;
+    });
 }
 
 extern "C" int qzd_zstd_encode_frames(qzd_ctx *c, const uint8_t *d_literals, const uint32_t *d_seqs, const uint32_t *h_desc,
@@ -1373,10 +1359,6 @@ extern "C" int qzd_zstd_encode_frames(qzd_ctx *c, const uint8_t *d_literals, con
     if (dst_cap < bound) { snprintf(c->err, sizeof(c->err), "destination too small"); return QZD_ERR_DSTCAP; }
     hipSetDevice(c->device);
     const uint32_t stride = qzd_zs_stride(maxc);
-    QZD_TRY(reserve_call_arrays(c, nframes));
-    uint32_t batch = nframes < 16384u ? nframes : 16384u;
-    if ((uint64_t)batch * stride > (1ull << 30)) batch = (uint32_t)((1ull << 30) / stride);
-    QZD_TRY(grow_dev(c, (void **)&c->lz4_slots, &c->slot_cap, (size_t)batch * stride));
     /* d_lane: the descriptions, then the word a wave sets when it meets records that are not a frame's */
     const size_t descb = ((size_t)nframes * sizeof(qzk_zs_fdesc) + 15) & ~(size_t)15;
     QZD_TRY(grow_dev(c, (void **)&c->d_lane, &c->lane_cap, descb + 16));
@@ -1384,27 +1366,26 @@ extern "C" int qzd_zstd_encode_frames(qzd_ctx *c, const uint8_t *d_literals, con
     uint32_t *d_bad = (uint32_t *)(c->d_lane + descb);
     hipStream_t st = c->st[0];
     const uint32_t cus = c->cus ? c->cus : 256u;
-    QZD_TRY(call_begin(c, st, nframes, c->nbatches));
-    HIPCHK(c, hipMemcpyAsync(d_fd, fd.data(), (size_t)nframes * sizeof(qzk_zs_fdesc), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemsetAsync(d_bad, 0, 4, st));
-    for (uint32_t b = 0; b < nframes; b += batch) {
-        const uint32_t bn = nframes - b < batch ? nframes - b : batch;
+    uint32_t bad = 0;
+    QZD_TRY(slot_rounds(c, nframes, stride, qzd_slot_batch(nframes, stride, QZD_SLOT_GIGABYTE), d_dst, dst_cap, h_out_len, NULL, [&](uint32_t b, uint32_t bn, uint8_t *slots) -> int {
+        if (b == 0) {                                               /* the call's first launches: the descriptions, the word cleared */
+            HIPCHK(c, hipMemcpyAsync(d_fd, fd.data(), (size_t)nframes * sizeof(qzk_zs_fdesc), hipMemcpyHostToDevice, st));
+            HIPCHK(c, hipMemsetAsync(d_bad, 0, 4, st));
+        }
         HIPCHK(c, hipMemsetAsync(c->k1_counter, 0, 4, st));
         hipLaunchKernelGGL(qzk_zstd_encode_kernel, dim3(std::min<uint32_t>(bn, QZD_ZS_WPC * cus)), dim3(64), 0, st, d_literals,
-                           (const qzk_zs_seq *)d_seqs, d_fd + b, bn, c->lz4_slots, stride, c->d_len + b, d_bad, c->k1_counter);
-        launch_scan_gather(c, st, c->lz4_slots, stride, b, bn, d_dst, dst_cap);
-    }
-    HIPCHK(c, hipEventRecord(c->ev_end, st));
-    QZD_TRY(publish_totals(c, st));
-    uint32_t bad = 0;
-    HIPCHK(c, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st));       /* fd outlives the copy: finish_sync_call waits for st */
-    QZD_TRY(finish_sync_call(c, st, h_out_len));
+                           (const qzk_zs_seq *)d_seqs, d_fd + b, bn, slots, stride, c->d_len + b, d_bad, c->k1_counter);
+        return QZD_OK;
+    }, [&]() -> int {                                               /* fd and bad outlive the copies: the driver waits for st */
+        HIPCHK(c, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st));
+        return QZD_OK;
+    }));
     if (bad) {
         *h_out_len = 0;
         snprintf(c->err, sizeof(c->err), "zstd: records that are not a frame's (lengths, an offset, or a match below 3)");
         return QZD_ERR_DATA;
     }
-    if (h_frame_len) HIPCHK(c, hipMemcpy(h_frame_len, c->d_len, (size_t)nframes * 4, hipMemcpyDeviceToHost));
+    if (h_frame_len) HIPCHK(c, hipMemcpy(h_frame_len, c->d_len, (size_t)nframes * 4, hipMemcpyDeviceToHost));      /* only of frames that are good */
     return QZD_OK;
 }
 

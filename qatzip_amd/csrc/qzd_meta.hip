@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "qzd_internal.h"
+#include "qz_frame.h"
 #include "qzk_meta.h"
 
 static const qzd_crccfg k_crc32_gzip = {0x04C11DB7ull, 0xFFFFFFFFull, 1, 1, 0xFFFFFFFFull};
@@ -107,7 +108,7 @@ extern "C" int qzd_blocks_compress(qzd_ctx *c, const uint8_t *d_src, uint64_t n,
     const uint32_t nb = (uint32_t)nb64;
     hipSetDevice(c->device);
     /* scratch: the slot streams back to back (worst case: stored deflate blocks), the plan, the ranges, hash and CRCs */
-    const uint64_t worst = n + (uint64_t)nb * (5ull * (block_sz / 32767 + 2) + 16) + 64;
+    const uint64_t worst = qz_deflate_bound(n, nb, block_sz);
     const size_t need = carved(worst + 64) + carved((size_t)nb * sizeof(qzk_blockpos)) + carved((size_t)nb * 8) +
                         2 * carved((size_t)nb * sizeof(qzk_mrange)) + carved((size_t)nb * 4) + 4 * carved((size_t)nb * 8) + 256;
     int rc = meta_reserve(c, need);

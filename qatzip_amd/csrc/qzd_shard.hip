@@ -24,6 +24,7 @@
 #include <new>
 
 #include "qzd_internal.h"
+#include "qz_frame.h"
 
 typedef struct { uint64_t raw_len, comp_len; uint32_t crc, seq, done, pad; } qzd_shard_rec;    /* 32 bytes */
 
@@ -203,11 +204,8 @@ extern "C" int qzd_shard_put(qzd_shard *s, const uint8_t *d_comp, uint64_t comp_
  * gzip header does: 4 = fastest, 2 = best, 0 otherwise) and its trailer */
 static void member_frame(unsigned char hdr[24], unsigned char tr[8], int level, uint64_t raw, uint64_t comp, uint32_t crc)
 {
-    static const unsigned char h0[24] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 4, 255, 12, 0, 'Q', 'Z', 8, 0};
-    memcpy(hdr, h0, 24);
-    hdr[8] = level == 9 ? 2 : level < 2 ? 4 : 0;
-    for (int i = 0; i < 4; i++) { hdr[16 + i] = (unsigned char)(raw >> (8 * i)); hdr[20 + i] = (unsigned char)(comp >> (8 * i)); }
-    for (int i = 0; i < 4; i++) { tr[i] = (unsigned char)(crc >> (8 * i)); tr[4 + i] = (unsigned char)(raw >> (8 * i)); }
+    qz_member_open(hdr, F_GZIP_EXT, level, false);
+    qz_member_close(hdr, tr, F_GZIP_EXT, crc, (uint32_t)raw, (uint32_t)comp);
 }
 
 extern "C" int qzd_shard_finish(qzd_shard *s, uint32_t seq, double timeout_s, int level, uint8_t **d_stream, uint64_t *stream_len,
