@@ -304,6 +304,25 @@ int qzd_lz4_decompress_frames(qzd_ctx *ctx, const uint8_t *d_comp, uint8_t *d_ou
  * (today auto and 2 qualify the same frames).  A context starts with QATZIP_AMD_LZ4D=auto|wave|blocks. */
 int qzd_lz4_decode_route(qzd_ctx *ctx, int route);
 
+/* decode nsegs zstd frames (RFC 8878 without dictionaries: any frame header, any number of Raw, RLE and Compressed blocks,
+ * every literals type and sequence mode, repeat offsets, the content checksum verified on the GPU) and skippable frames
+ * (magic 0x184D2A50 - 5F: in_used is their length, out_len 0); replaces the ZSTD_decompressStream loop of the reference's
+ * qzstd (utils/qzstd.c:441-510).  h_segs / h_res are qzd_lz4seg / qzd_lz4res, the contract of qzd_lz4_decompress_frames:
+ * frame i is in_len bytes at d_comp + in_off and may write out_cap bytes at d_out + out_off.  Per frame the answer is
+ * {0, in_used, out_len} or a status:
+ *   -1 malformed (anything RFC 8878 forbids: INTEGRATION.md, "Zstd sessions", lists the refusals)
+ *   -2 the frame's output is beyond out_cap (known from Frame_Content_Size before a byte is written, else when it happens)
+ *   -3 truncated: the input ends inside the frame
+ *   -4 content checksum mismatch (the output has been written)
+ *   -5 unsupported: a dictionary id, a content size above 32 bits
+ * in_used / out_len of a failed frame are 0 (of a checksum mismatch: the frame's).  Nothing is loaded beyond a frame's in_len
+ * or stored beyond its out_cap.  Two stages (qzk_zstdd.h): the bit streams, four frames a wave, into per-frame scratch
+ * - about 5 bytes per byte of out_cap and 4 per byte of input - then the copy engine of the inflate, a wave per frame.  The
+ * frames are taken in rounds whose scratch stays under 2 GiB (a frame that needs more is a round of its own); three
+ * launches per round, whatever nsegs.  A frame's blocks are serial on its lanes: one huge frame is correct but slow. */
+int qzd_zstd_decompress_frames(qzd_ctx *ctx, const uint8_t *d_comp, uint8_t *d_out, const void *h_segs,
+                               uint32_t nsegs, void *h_res);
+
 /* ------------------------------------------------------------------ one member from several GPUs
  *
  * What is left of the reference's in-order retire (doCompressOut: payload copy + crc32_combine + footer,

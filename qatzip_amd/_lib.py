@@ -76,6 +76,7 @@ def load(build_if_missing=True):
     L.qzd_zstd_bound.argtypes = [C.c_uint64, C.c_uint32]; L.qzd_zstd_bound.restype = C.c_uint64
     L.qzd_zstd_compress_frames.argtypes = L.qzd_lz4s_compress_blocks.argtypes
     L.qzd_zstd_encode_frames.argtypes = [vp, u8p, vp, vp, C.c_uint32, u8p, C.c_uint64, C.POINTER(C.c_uint64), vp]
+    L.qzd_zstd_decompress_frames.argtypes = [vp, u8p, u8p, vp, C.c_uint32, vp]
     L.qzd_chunk_lens.argtypes = [vp, vp, C.c_uint32]
     L.qzd_shard_root_create.argtypes = [vp, C.c_uint32, C.c_uint64, C.c_char_p, C.POINTER(vp)]
     L.qzd_shard_attach.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_char_p, C.c_uint64, C.POINTER(vp)]
@@ -125,7 +126,7 @@ def exported_symbols():
             "qzd_shard_attach", "qzd_shard_slot_handle", "qzd_shard_attach_slot", "qzd_lz4_compress_linked", "qzd_shard_put", "qzd_shard_finish", "qzd_shard_close", "qzd_crc32_combine",
             "qzd_lz4hc_compress_frames", "qzd_lz4hc_compress_frames_hw", "qzd_lz4hc_compress_linked",
             "qzd_lz4s_bound", "qzd_lz4s_compress_blocks",
-            "qzd_zstd_bound", "qzd_zstd_compress_frames", "qzd_zstd_encode_frames",
+            "qzd_zstd_bound", "qzd_zstd_compress_frames", "qzd_zstd_encode_frames", "qzd_zstd_decompress_frames",
             "qzd_crcn_ranges", "qzd_xxh32_ranges", "qzd_blocks_compress", "qzd_blocks_decompress",
             "qzd_crc32_fold", "qzd_pcie_peak", "qzd_rccl_unique_id", "qzd_rccl_create", "qzd_rccl_gather", "qzd_rccl_close"]
 
@@ -366,6 +367,14 @@ class Context:
         sa = np.array([tuple(s) for s in segs], dtype=LZ4SEG_DT)
         res = np.zeros(len(segs), LZ4RES_DT)
         self._chk(self.L.qzd_lz4_decompress_frames(self.h, d_comp.ptr, d_out.ptr, sa.ctypes.data, len(segs), res.ctypes.data))
+        return res
+
+    def zstd_decompress_frames(self, d_comp, d_out, segs):
+        """zstd and skippable frames; segs: list of (in_off, out_off, in_len, out_cap) -> structured results (status,
+        in_used, out_len): 0, or -1 malformed, -2 beyond out_cap, -3 truncated, -4 content checksum, -5 unsupported"""
+        sa = np.array([tuple(s) for s in segs], dtype=LZ4SEG_DT)
+        res = np.zeros(len(segs), LZ4RES_DT)
+        self._chk(self.L.qzd_zstd_decompress_frames(self.h, d_comp.ptr, d_out.ptr, sa.ctypes.data, len(segs), res.ctypes.data))
         return res
 
     def inflate_timing(self):

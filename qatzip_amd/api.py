@@ -100,6 +100,7 @@ def lib():
         L.qzGetDefaultsLZ4.argtypes = [P(QzSessionParamsLZ4)]
         L.qzSetupSessionLZ4S.argtypes = [P(QzSession), P(QzSessionParamsLZ4S)]
         L.qzSetupSessionZstdAMD.argtypes = [P(QzSession), P(QzSessionParamsLZ4S)]
+        L.qzSetupSessionZstdDecAMD.argtypes = [P(QzSession), P(QzSessionParamsLZ4S)]
         L.qzGetDefaultsLZ4S.argtypes = [P(QzSessionParamsLZ4S)]
         L.qzSetDefaultsLZ4S.argtypes = [P(QzSessionParamsLZ4S)]
         L.qzCompressExt.argtypes = [P(QzSession), u8p, up, C.c_void_p, up, C.c_uint, P(C.c_uint64)]
@@ -185,11 +186,11 @@ class Session:
 
     def __init__(self, data_fmt=QZ_DEFLATE_GZIP_EXT, hw_buff_sz=65536, comp_lvl=1, lz4=False, strm_buff_sz=None,
                  zlib_format=False, stop_at_stream_end=False, lz4s=False, mini_match=3, callback=None, external=None,
-                 zstd=False):
+                 zstd=False, zstd_dec=None):
         self.L = lib()
         self.s = QzSession()
         self.cb = None
-        if lz4s or zstd:
+        if lz4s or zstd or zstd_dec is not None:
             # an LZ4s session (qzSetupSessionLZ4S): compress only; callback is a Python callable with qzLZ4SCallbackFn's
             # arguments (or a QzLZ4SCallback), kept alive by this object for as long as the session may call it
             p = QzSessionParamsLZ4S(); self.L.qzGetDefaultsLZ4S(C.byref(p))
@@ -202,6 +203,10 @@ class Session:
             p.qzCallback_external = external
             # zstd: a zstd session (qzSetupSessionZstdAMD, include/qzamd_zstd.h) - the same parameters, a zstd frame per chunk
             setup = self.L.qzSetupSessionZstdAMD if zstd else self.L.qzSetupSessionLZ4S
+            # zstd_dec: a zstd decode session (qzSetupSessionZstdDecAMD, include/qzamd_zstd_dec.h) with that direction
+            if zstd_dec is not None:
+                p.common_params.direction = zstd_dec
+                setup = self.L.qzSetupSessionZstdDecAMD
             self.rc_setup = setup(C.byref(self.s), C.byref(p))
         elif zlib_format or stop_at_stream_end:  # qzSetupSessionDeflateExt: zlib_format = 1 is the RFC 1950 wrapper with an Adler-32 trailer
             p = QzSessionParamsDeflateExt(); self.L.qzGetDefaultsDeflateExt(C.byref(p))

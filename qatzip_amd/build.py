@@ -17,6 +17,7 @@ def _sources():
     out.append(os.path.join(HERE, "cli", "qzstd_amd.c"))
     out.append(os.path.join(os.path.dirname(HERE), "include", "qzamd_device.h"))
     out.append(os.path.join(os.path.dirname(HERE), "include", "qzamd_zstd.h"))
+    out.append(os.path.join(os.path.dirname(HERE), "include", "qzamd_zstd_dec.h"))
     q = os.path.join(os.path.dirname(HERE), "include", "qatzip.h")
     if os.path.exists(q):
         out.append(q)
@@ -59,7 +60,7 @@ def build_cli(verbose=False):
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
-    # qzstd-amd: the compress path of the reference's qzstd on a zstd session (include/qzamd_zstd.h)
+    # qzstd-amd: the reference's qzstd on a zstd session (include/qzamd_zstd.h) and a decode session (qzamd_zstd_dec.h)
     cmd = ["gcc", "-O2", "-std=gnu99", "-Wall", "-I", os.path.join(os.path.dirname(HERE), "include"),
            os.path.join(HERE, "cli", "qzstd_amd.c"), "-o", ZSTD_CLI, "-L", HERE, "-lqatzip_amd", "-Wl,-rpath,$ORIGIN"]
     if verbose:

@@ -33,6 +33,8 @@
 #include "../../include/qatzip.h"
 #include "../../include/qzamd_device.h"
 #include "../../include/qzamd_zstd.h"
+#include "../../include/qzamd_zstd_dec.h"
+#include "qzd_zstdd_host.h"             /* a zstd frame's extent */
 #include "qz_frame.h"                   /* the F_* formats, bounds, the delivery rule, member framing, the crc folds */
 
 struct Params {
@@ -41,6 +43,7 @@ struct Params {
     req_cnt_thrshold, wait_cnt_thrshold; QzPollingMode_T polling_mode; unsigned is_sensitive_mode;
     unsigned char stop_at_stream_end, zlib_format; qzLZ4SCallbackFn cb; void *cb_ext; unsigned lz4s_mini_match;
     bool zstd;                      /* an F_LZ4S session made by qzSetupSessionZstdAMD: the same parse, written as zstd frames */
+    bool zstd_dec;                  /* ... made by qzSetupSessionZstdDecAMD: qzDecompress reads zstd frames */
 };
 
 struct Sess {
@@ -155,7 +158,7 @@ static int lz4s_to(Params &p, const QzSessionParamsLZ4S_T *s)
     if (s->lz4s_mini_match < 3 || s->lz4s_mini_match > 4) return QZ_PARAMS;
     p = g_def;
     from_common(p, s->common_params);
-    p.fmt = F_LZ4S; p.zstd = false;
+    p.fmt = F_LZ4S; p.zstd = false; p.zstd_dec = false;
     p.cb = s->qzCallback; p.cb_ext = s->qzCallback_external; p.lz4s_mini_match = s->lz4s_mini_match;
     return check_common(p, true);
 }
@@ -336,6 +339,23 @@ extern "C" int qzSetupSessionZstdAMD(QzSession_T *sess, QzSessionParamsLZ4S_T *p
     if (lz4s_to(p, params) != QZ_OK) return QZ_PARAMS;
     if (p.hw_buff_sz > 128 * 1024 || p.cb) return QZ_PARAMS;
     p.zstd = true;
+    return make_session(sess, p);
+}
+
+/* a zstd decode session (include/qzamd_zstd_dec.h): the checks of qzSetupSessionZstdAMD, but the direction is
+ * QZ_DIR_DECOMPRESS or QZ_DIR_BOTH - QZ_DIR_COMPRESS is what the older call is for.  The compress side is that call's */
+extern "C" int qzSetupSessionZstdDecAMD(QzSession_T *sess, QzSessionParamsLZ4S_T *params)
+{
+    QzSessionParamsLZ4S_T tmp; Params p;
+    if (!sess) return QZ_PARAMS;
+    if (params) tmp = *params;
+    else { qzGetDefaultsLZ4S(&tmp); tmp.common_params.comp_algorithm = QZ_LZ4s; }
+    const QzDirection_T dir = tmp.common_params.direction;
+    if (dir != QZ_DIR_DECOMPRESS && dir != QZ_DIR_BOTH) return QZ_PARAMS;
+    tmp.common_params.direction = QZ_DIR_COMPRESS;                  /* (what an LZ4s session's checks ask for) */
+    if (lz4s_to(p, &tmp) != QZ_OK) return QZ_PARAMS;
+    if (p.hw_buff_sz > 128 * 1024 || p.cb) return QZ_PARAMS;
+    p.direction = dir; p.zstd = true; p.zstd_dec = true;
     return make_session(sess, p);
 }
 
@@ -707,6 +727,48 @@ static int decompress_lz4(QzSession_T *sess, Sess *s, const unsigned char *src, 
     return deliver(sess, src_len, dest_len, ti, produced, QZ_OK);
 }
 
+/* a zstd decode session: decompress_lz4's contract over zstd and skippable frames (qzd_zstdd_host.h for the extents).  A
+ * frame of unknown content size gets the rest of dest, capped by its bound, and is decoded alone */
+static int decompress_zstd(QzSession_T *sess, Sess *s, const unsigned char *src, unsigned int *src_len,
+                           unsigned char *dest, unsigned int *dest_len)
+{
+    const uint32_t n = *src_len, cap = *dest_len;
+    *src_len = 0; *dest_len = 0;
+    s->out_resident = false;
+    std::vector<qzd_lz4seg> segs;
+    uint32_t ti = 0; uint64_t to = 0;
+    bool alone = false;
+    while (ti < n && to < cap) {
+        uint64_t content, bound; bool hc;
+        int64_t ext = qzd_zd_frame_extent(src + ti, n - ti, &content, &hc, &bound);
+        if (ext < 0) {
+            if (segs.empty()) return QZ_FAIL;
+            break;                                                  /* complete frames first; the caller comes back with the rest */
+        }
+        if (!hc) content = std::min<uint64_t>(cap - to, bound);     /* unknown: the rest, as far as the blocks can reach */
+        if (to + content > cap) { if (segs.empty()) return QZ_BUF_ERROR; break; }
+        qzd_lz4seg g; g.in_off = ti; g.out_off = to; g.in_len = (uint32_t)ext; g.out_cap = (uint32_t)content;
+        segs.push_back(g);
+        ti += (uint32_t)ext; to += content;
+        if (!hc) { alone = true; break; }                           /* sizes unknown beyond this frame: one at a time */
+    }
+    if (segs.empty()) return QZ_OK;
+    int rc = reserve(s, n, cap);
+    if (rc) return rc;
+    if (qzd_h2d(s->ctx, s->d_in, src, ti) != QZD_OK) return QZ_FAIL;
+    std::vector<qzd_lz4res> res(segs.size());
+    if (qzd_zstd_decompress_frames(s->ctx, s->d_in, s->d_out, segs.data(), (uint32_t)segs.size(), res.data()) != QZD_OK) return QZ_FAIL;
+    uint64_t produced = 0;
+    for (size_t i = 0; i < segs.size(); i++) {
+        if (res[i].status != 0 || res[i].in_used != segs[i].in_len) return QZ_FAIL;
+        if (!(alone && i + 1 == segs.size()) && res[i].out_len != segs[i].out_cap) return QZ_FAIL;
+        produced = segs[i].out_off + res[i].out_len;
+    }
+    if (produced && qzd_d2h(s->ctx, dest, s->d_out, produced) != QZD_OK) return QZ_FAIL;
+    s->out_resident = true;
+    return deliver(sess, src_len, dest_len, ti, produced, QZ_OK);
+}
+
 /* Small synchronous calls from many threads share launches too (below: sync_via_queue) */
 static bool sync_via_queue(QzSession_T *sess, Sess *s, const unsigned char *src, unsigned int *src_len, unsigned char *dest,
                            unsigned int *dest_len, unsigned long *crc, bool compress, int *rc_out);
@@ -994,6 +1056,8 @@ static int decompress_direct(QzSession_T *sess, const unsigned char *src, unsign
         goto fail;
     }
     if (s->p.fmt == F_LZ4) rc = decompress_lz4(sess, s, src, src_len, dest, dest_len);
+    /* qzDecompress2 and the Crc64 calls (may_queue false) answer for a zstd decode session what they do for every LZ4s session */
+    else if (s->p.fmt == F_LZ4S && s->p.zstd_dec && may_queue) rc = decompress_zstd(sess, s, src, src_len, dest, dest_len);
     else if (s->p.fmt == F_LZ4S) rc = QZ_UNSUPPORTED_FMT;
     else rc = decompress_deflate(sess, s, src, src_len, dest, dest_len, crc);
     sess->thd_sess_stat = rc;
