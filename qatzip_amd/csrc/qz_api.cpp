@@ -36,6 +36,7 @@
 #include "../../include/qzamd_zstd_dec.h"
 #include "qzd_zstdd_host.h"             /* a zstd frame's extent */
 #include "qz_frame.h"                   /* the F_* formats, bounds, the delivery rule, member framing, the crc folds */
+#include "qz_unframe.h"                 /* ... and of the decompress calls: member headers, sized members, frame plans, the crc folds */
 
 struct Params {
     QzHuffmanHdr_T huffman_hdr; QzDirection_T direction; int fmt; unsigned comp_lvl; unsigned char comp_algorithm;
@@ -456,8 +457,6 @@ static int reserve(Sess *s, size_t in_n, size_t out_n)
     return QZ_OK;
 }
 
-static uint32_t rd16(const unsigned char *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8; }
-
 /* ------------------------------------------------------------------ compress */
 static bool pinned_span(const void *p, size_t len);
 /* the end of every call that came somewhere: the lengths and the session's totals */
@@ -665,108 +664,29 @@ static int compress_lz4(QzSession_T *sess, Sess *s, const unsigned char *src, un
     return deliver(sess, src_len, dest_len, n, produced, QZ_OK);
 }
 
-/* walk one LZ4 frame on the host: total frame length and (if present) content size; <0 on malformed input */
-static int64_t lz4_frame_extent(const unsigned char *p, uint32_t n, uint64_t *content, bool *has_content)
-{
-    if (n < 7 || rd32(p) != 0x184D2204u) return -1;
-    unsigned flg = p[4];
-    if ((flg >> 6) != 1) return -1;
-    uint32_t pos = 6;
-    *has_content = (flg >> 3) & 1; *content = 0;
-    if (*has_content) { if (n < 14) return -1; *content = (uint64_t)rd32(p + 6) | (uint64_t)rd32(p + 10) << 32; pos += 8; }
-    if (flg & 1) pos += 4;
-    pos += 1;
-    for (;;) {
-        if (pos + 4 > n) return -1;
-        uint32_t bh = rd32(p + pos); pos += 4;
-        if (bh == 0) break;
-        uint32_t bsz = bh & 0x7fffffffu;
-        if (bsz > n - pos) return -1;
-        pos += bsz + ((flg >> 4) & 1 ? 4 : 0);
-    }
-    if ((flg >> 2) & 1) { if (pos + 4 > n) return -1; pos += 4; }
-    return pos;
-}
-
-static int decompress_lz4(QzSession_T *sess, Sess *s, const unsigned char *src, unsigned int *src_len,
-                          unsigned char *dest, unsigned int *dest_len)
+/* LZ4 sessions and zstd decode sessions: the leading frames that fit (qz_frame_plan), a wave or more per frame in one launch.
+ * extent / run / may_be_short are the codec: lz4_frame_extent, qzd_lz4_decompress_frames, QZ_SHORT_LAST, or
+ * qzd_zd_frame_extent over zstd and skippable frames, qzd_zstd_decompress_frames, QZ_SHORT_LAST_UNSIZED */
+typedef int (*FramesFn)(qzd_ctx *ctx, const uint8_t *d_comp, uint8_t *d_out, const void *h_segs, uint32_t nsegs, void *h_res);
+static int decompress_frames(QzSession_T *sess, Sess *s, const unsigned char *src, unsigned int *src_len, unsigned char *dest,
+                             unsigned int *dest_len, QzExtentFn extent, FramesFn run, QzShortRule may_be_short)
 {
     const uint32_t n = *src_len, cap = *dest_len;
     *src_len = 0; *dest_len = 0;
     s->out_resident = false;
-    std::vector<qzd_lz4seg> segs;
-    uint32_t ti = 0; uint64_t to = 0;
-    while (ti < n && to < cap) {                                    /* frame loop, src/qatzip_sw.c:555-571 */
-        uint64_t content; bool hc;
-        int64_t ext = lz4_frame_extent(src + ti, n - ti, &content, &hc);
-        if (ext < 0) {                                              /* SW path: LZ4F error => QZ_FAIL */
-            if (segs.empty()) return QZ_FAIL;
-            break;                                                  /* complete frames first; the caller comes back with the rest */
-        }
-        if (!hc) content = cap - to;                                /* unknown: give it the rest */
-        if (to + content > cap) { if (segs.empty()) return QZ_BUF_ERROR; break; }
-        qzd_lz4seg g; g.in_off = ti; g.out_off = to; g.in_len = (uint32_t)ext; g.out_cap = (uint32_t)content;
-        segs.push_back(g);
-        ti += (uint32_t)ext; to += content;
-        if (!hc) break;                                             /* sizes unknown beyond this frame: one at a time */
-    }
-    if (segs.empty()) return QZ_OK;
-    int rc = reserve(s, n, cap);
+    QzFramePlan pl;
+    int rc = qz_frame_plan(extent, src, n, cap, &pl);
+    if (rc || pl.segs.empty()) return rc;
+    rc = reserve(s, n, cap);
     if (rc) return rc;
-    if (qzd_h2d(s->ctx, s->d_in, src, ti) != QZD_OK) return QZ_FAIL;
-    std::vector<qzd_lz4res> res(segs.size());
-    if (qzd_lz4_decompress_frames(s->ctx, s->d_in, s->d_out, segs.data(), (uint32_t)segs.size(), res.data()) != QZD_OK) return QZ_FAIL;
-    uint64_t produced = 0;
-    for (size_t i = 0; i < segs.size(); i++) {
-        if (res[i].status != 0 || res[i].in_used != segs[i].in_len) return QZ_FAIL;
-        if (i + 1 < segs.size() && res[i].out_len != segs[i].out_cap) return QZ_FAIL;
-        produced = segs[i].out_off + res[i].out_len;
-    }
-    if (produced && qzd_d2h(s->ctx, dest, s->d_out, produced) != QZD_OK) return QZ_FAIL;
+    if (qzd_h2d(s->ctx, s->d_in, src, pl.ti) != QZD_OK) return QZ_FAIL;
+    std::vector<qzd_lz4res> res(pl.segs.size());
+    if (run(s->ctx, s->d_in, s->d_out, pl.segs.data(), (uint32_t)pl.segs.size(), res.data()) != QZD_OK) return QZ_FAIL;
+    const int64_t produced = qz_frames_produced(pl.segs.data(), res.data(), pl.segs.size(), pl.alone, may_be_short);
+    if (produced < 0) return QZ_FAIL;
+    if (produced && qzd_d2h(s->ctx, dest, s->d_out, (uint64_t)produced) != QZD_OK) return QZ_FAIL;
     s->out_resident = true;
-    return deliver(sess, src_len, dest_len, ti, produced, QZ_OK);
-}
-
-/* a zstd decode session: decompress_lz4's contract over zstd and skippable frames (qzd_zstdd_host.h for the extents).  A
- * frame of unknown content size gets the rest of dest, capped by its bound, and is decoded alone */
-static int decompress_zstd(QzSession_T *sess, Sess *s, const unsigned char *src, unsigned int *src_len,
-                           unsigned char *dest, unsigned int *dest_len)
-{
-    const uint32_t n = *src_len, cap = *dest_len;
-    *src_len = 0; *dest_len = 0;
-    s->out_resident = false;
-    std::vector<qzd_lz4seg> segs;
-    uint32_t ti = 0; uint64_t to = 0;
-    bool alone = false;
-    while (ti < n && to < cap) {
-        uint64_t content, bound; bool hc;
-        int64_t ext = qzd_zd_frame_extent(src + ti, n - ti, &content, &hc, &bound);
-        if (ext < 0) {
-            if (segs.empty()) return QZ_FAIL;
-            break;                                                  /* complete frames first; the caller comes back with the rest */
-        }
-        if (!hc) content = std::min<uint64_t>(cap - to, bound);     /* unknown: the rest, as far as the blocks can reach */
-        if (to + content > cap) { if (segs.empty()) return QZ_BUF_ERROR; break; }
-        qzd_lz4seg g; g.in_off = ti; g.out_off = to; g.in_len = (uint32_t)ext; g.out_cap = (uint32_t)content;
-        segs.push_back(g);
-        ti += (uint32_t)ext; to += content;
-        if (!hc) { alone = true; break; }                           /* sizes unknown beyond this frame: one at a time */
-    }
-    if (segs.empty()) return QZ_OK;
-    int rc = reserve(s, n, cap);
-    if (rc) return rc;
-    if (qzd_h2d(s->ctx, s->d_in, src, ti) != QZD_OK) return QZ_FAIL;
-    std::vector<qzd_lz4res> res(segs.size());
-    if (qzd_zstd_decompress_frames(s->ctx, s->d_in, s->d_out, segs.data(), (uint32_t)segs.size(), res.data()) != QZD_OK) return QZ_FAIL;
-    uint64_t produced = 0;
-    for (size_t i = 0; i < segs.size(); i++) {
-        if (res[i].status != 0 || res[i].in_used != segs[i].in_len) return QZ_FAIL;
-        if (!(alone && i + 1 == segs.size()) && res[i].out_len != segs[i].out_cap) return QZ_FAIL;
-        produced = segs[i].out_off + res[i].out_len;
-    }
-    if (produced && qzd_d2h(s->ctx, dest, s->d_out, produced) != QZD_OK) return QZ_FAIL;
-    s->out_resident = true;
-    return deliver(sess, src_len, dest_len, ti, produced, QZ_OK);
+    return deliver(sess, src_len, dest_len, pl.ti, (uint64_t)produced, QZ_OK);
 }
 
 /* Small synchronous calls from many threads share launches too (below: sync_via_queue) */
@@ -836,57 +756,17 @@ extern "C" int qzCompressCrc(QzSession_T *sess, const unsigned char *src, unsign
 { return qzCompressCrcExt(sess, src, src_len, dest, dest_len, last, crc, NULL); }
 
 /* ------------------------------------------------------------------ decompress */
-/* parse one member header at p[0..n): returns payload offset or a negative QZ_* code;
- * for gzip-ext also the sizes its extra field carries (0 when absent) */
-static int parse_header(int fmt, const unsigned char *p, uint32_t n, uint32_t *ext_src, uint32_t *ext_dst)
-{
-    *ext_src = *ext_dst = 0;
-    if (fmt == F_RAW) return 0;
-    if (fmt == F_4B) return n >= 4 ? 4 : QZ_DATA_ERROR;
-    if (fmt == F_ZLIB) {
-        if (n < 2 || (p[0] & 0x0f) != 8 || ((p[0] << 8 | p[1]) % 31) || (p[1] & 0x20)) return QZ_DATA_ERROR;
-        return 2;
-    }
-    if (n < 10 || p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || (p[3] & 0xe0)) return QZ_DATA_ERROR;
-    uint32_t pos = 10; unsigned flg = p[3];
-    if (flg & 4) {
-        if (pos + 2 > n) return QZ_DATA_ERROR;
-        uint32_t xl = rd16(p + pos);
-        if (pos + 2 + xl > n) return QZ_DATA_ERROR;
-        if (xl == 12 && p[pos + 2] == 'Q' && p[pos + 3] == 'Z' && rd16(p + pos + 4) == 8) { *ext_src = rd32(p + pos + 6); *ext_dst = rd32(p + pos + 10); }
-        pos += 2 + xl;
-    }
-    if (flg & 8) { while (pos < n && p[pos]) pos++; pos++; }
-    if (flg & 16) { while (pos < n && p[pos]) pos++; pos++; }
-    if (flg & 2) pos += 2;
-    return pos <= n ? (int)pos : QZ_DATA_ERROR;
-}
-
 /* Streams written by the reference's HARDWARE path (and by per-chunk callers of either path) are one gzip-ext member
  * per hw_buff_sz chunk, each header carrying both sizes (qzGzipHeaderGen, src/qatzip_gzip.c:86-118; the engine walks
  * them the same way in checkHeader, src/qatzip_utils.c:1232-1345).  The member boundaries are therefore known without
- * decoding anything: hop header to header on the host, then inflate every member as one segment of a single launch and
- * check all trailers with one CRC launch - the batch the QAT engine keeps in flight, made as wide as the call.
+ * decoding anything: hop header to header on the host (qz_sized_walk), then inflate every member as one segment of a single
+ * launch and check all trailers with one CRC launch - the batch the QAT engine keeps in flight, made as wide as the call.
  * Returns the number of members done (0 = not this kind of stream, the member loop takes over), < 0 on error. */
 static int decompress_sized_members(Sess *s, const unsigned char *src, uint32_t n, uint32_t cap, uint32_t *ti_out,
                                     uint32_t *to_out, unsigned long *crc, bool *resident)
 {
-    struct Mem { uint32_t pay, csz, usz; };
-    std::vector<Mem> mem;
-    uint32_t pos = 0; uint64_t out = 0;
-    while (pos < n) {
-        uint32_t es = 0, ed = 0;
-        const int hl = parse_header(F_GZIP_EXT, src + pos, n - pos, &es, &ed);
-        if (hl < 0 || es == 0 || ed == 0) break;                    /* not a sized member (e.g. a software-path stream) */
-        if ((uint64_t)pos + hl + ed + 8 > n) break;                 /* cut short: the caller comes back with more */
-        if (out + es > cap) break;                                  /* destination full: whole members only */
-        if (es > 512u * 1024u) break;                               /* larger than any hw_buff_sz: a multi-chunk member of the software
-                                                                     * path (qzCompress fills the sizes in for those too) - the member loop
-                                                                     * below cuts it at its flush markers */
-        Mem m = { pos + (uint32_t)hl, ed, es };
-        mem.push_back(m);
-        pos += (uint32_t)hl + ed + 8; out += es;
-    }
+    std::vector<QzSized> mem;
+    qz_sized_walk(src, n, cap, &mem);
     if (mem.size() < 2) return 0;
     const uint32_t nm = (uint32_t)mem.size();
     std::vector<qzd_infseg> segs(nm);
@@ -894,22 +774,15 @@ static int decompress_sized_members(Sess *s, const unsigned char *src, uint32_t 
     std::vector<qzd_range> rg(nm);
     std::vector<uint32_t> c32(nm);
     uint64_t oo = 0;
-    for (uint32_t i = 0; i < nm; i++) {
-        segs[i].in_off = mem[i].pay; segs[i].in_len = mem[i].csz; segs[i].out_off = oo; segs[i].out_cap = mem[i].usz;
-        segs[i].flags = 0; segs[i].pad = mem[i].csz;               /* exact compressed length: lets phase A split it */
-        rg[i].off = oo; rg[i].len = mem[i].usz; rg[i].pad = 0;
-        oo += mem[i].usz;
-    }
+    for (uint32_t i = 0; i < nm; i++) { qz_member_seg(&segs[i], &rg[i], mem[i].pay, mem[i].csz, oo, mem[i].usz); oo += mem[i].usz; }
     if (!*resident) { *resident = true; if (qzd_h2d(s->ctx, s->d_in, src, n) != QZD_OK) return QZ_FAIL; }
     if (qzd_inflate_segments(s->ctx, s->d_in, s->d_out, segs.data(), nm, res.data()) != QZD_OK) return QZ_FAIL;
     if (qzd_crc32_ranges(s->ctx, s->d_out, rg.data(), nm, c32.data()) != QZD_OK) return QZ_FAIL;
     uint32_t good = 0; uint64_t to = 0;
     for (; good < nm; good++) {
-        const Mem &m = mem[good];
-        const unsigned char *tr = src + m.pay + m.csz;
-        if (res[good].status != 0 || res[good].out_len != m.usz || res[good].in_used != m.csz) break;
-        if (rd32(tr) != c32[good] || rd32(tr + 4) != m.usz) break;
-        if (crc) *crc = (to == 0 && *crc == 0) ? c32[good] : qzd_crc32_combine((uint32_t)*crc, c32[good], m.usz);
+        const QzSized &m = mem[good];
+        if (!member_ok(res[good], c32[good], src + m.pay + m.csz, m.csz, m.usz)) break;
+        if (crc) qz_crc_fold_member(crc, to, c32[good], m.usz);
         to += m.usz;
     }
     /* a member that is not ONE deflate segment (several chunks behind one sized header, or damaged) ends the batch; when it
@@ -920,35 +793,115 @@ static int decompress_sized_members(Sess *s, const unsigned char *src, uint32_t 
     return (int)good;
 }
 
+/* A member whose output did not fit the caller's destination lies decoded in d_hold and goes out over as many calls as it
+ * takes: hold_begin the first piece, hold_next the others.  The buffer is had, and given up with its two lengths, here only. */
+static bool hold_alloc(Sess *s, uint64_t cap) { s->d_hold = (uint8_t *)qzd_dev_alloc(s->ctx, cap + 4096); return s->d_hold != NULL; }
+static void hold_release(Sess *s) { if (s->d_hold) qzd_dev_free(s->ctx, s->d_hold); s->d_hold = NULL; s->hold_len = s->hold_pos = 0; }
+/* the next k bytes of it to dest, their CRC-32 into *crc by the caller's rule */
+static int hold_piece(Sess *s, unsigned char *dest, uint32_t k, unsigned long *crc, void (*fold)(unsigned long *, uint32_t, uint64_t))
+{
+    uint32_t c = 0;
+    if (k && qzd_d2h(s->ctx, dest, s->d_hold + s->hold_pos, k) != QZD_OK) return QZ_FAIL;
+    if (crc && k && qzd_crc32(s->ctx, s->d_hold + s->hold_pos, k, &c) != QZD_OK) return QZ_FAIL;
+    if (crc && k) fold(crc, c, k);
+    s->hold_pos += k;
+    return QZ_OK;
+}
+/* the first piece of the ol bytes; everything but the member's last byte, at pos - 1, counts as consumed, so the caller keeps calling */
+static int hold_begin(QzSession_T *sess, Sess *s, uint64_t ol, uint32_t pos, unsigned int *src_len, unsigned char *dest,
+                      unsigned int *dest_len, uint32_t cap, unsigned long *crc)
+{
+    const uint32_t k = (uint32_t)std::min<uint64_t>(cap, ol);
+    s->hold_len = ol;
+    if (hold_piece(s, dest, k, crc, qz_crc_fold_lone) != QZ_OK) return QZ_FAIL;
+    return deliver(sess, src_len, dest_len, pos - 1, k, QZ_OK);
+}
+/* a later piece; the member's last input byte was held back for exactly this, and goes with the last piece */
+static int hold_next(QzSession_T *sess, Sess *s, unsigned int *src_len, unsigned char *dest, unsigned int *dest_len, unsigned long *crc)
+{
+    const uint32_t n = *src_len, cap = *dest_len;
+    const uint32_t k = (uint32_t)std::min<uint64_t>(cap, s->hold_len - s->hold_pos);
+    if (k == 0 && s->hold_pos < s->hold_len) { *src_len = 0; *dest_len = 0; return QZ_BUF_ERROR; }
+    if (hold_piece(s, dest, k, crc, qz_crc_fold_piece) != QZ_OK) return QZ_FAIL;
+    const bool last_piece = s->hold_pos == s->hold_len && n >= 1;   /* the held-back byte has to be there to be consumed */
+    if (last_piece) { hold_release(s); s->end_of_stream = 1; }
+    return deliver(sess, src_len, dest_len, last_piece ? 1 : 0, k, QZ_OK);
+}
+
+/* A device call's answer as a QZ_* code.  Only what the DATA is to blame for is a data error: a failed device call is QZ_FAIL,
+ * scratch that could not be had QZ_NOSW_LOW_MEM (there is no software path behind this library to go to).  `other` is the
+ * caller's answer to QZD_ERR_UNSUPPORTED: the deflate path blames the data, the metadata call does not. */
+static int qz_code(int r, int other)
+{
+    return r == QZD_OK ? QZ_OK : r == QZD_ERR_DSTCAP ? QZ_BUF_ERROR : r == QZD_ERR_NOMEM ? QZ_NOSW_LOW_MEM :
+           r == QZD_ERR_DATA ? QZ_DATA_ERROR : (r == QZD_ERR_HIP || r == QZD_ERR_PARAM) ? QZ_FAIL : other;
+}
+
 /* a member this large (compressed) is decoded piece by piece while it arrives: two pieces of qzd_inflate.hip's minimum */
 #define QZ_PIPE_MIN_BYTES (24u << 20)
+/* what became of one member's deflate stream: input used, output, its CRC-32, where the output lies (d_out + to, or d_hold when
+ * `held`), and whether the device layer has already put it into dest */
+struct Inflated { uint64_t iu, ol; uint32_t c32; int sent; bool held; uint8_t *obuf; };
+/* Inflate the stream at src[at..n) behind `to` bytes of output.  The source goes to the device when something needs it there: a
+ * large member is decoded WHILE it arrives (qzd_inflate_stream_from_host), everything else after one copy of the whole call. */
+static int inflate_member(Sess *s, const unsigned char *src, uint32_t n, uint32_t at, unsigned char *dest, uint32_t to, uint32_t cap,
+                          bool gz, bool want_crc, bool *resident, Inflated *m)
+{
+    int r;
+    uint32_t *const c32 = (gz || want_crc) ? &m->c32 : NULL;
+    m->iu = m->ol = 0; m->c32 = 0; m->sent = 0; m->held = false; m->obuf = s->d_out + to;
+    if (!*resident && n - at >= QZ_PIPE_MIN_BYTES) {
+        *resident = true;                                           /* (the bytes before this member's payload are never read on the device) */
+        r = qzd_inflate_stream_from_host(s->ctx, src + at, n - at, s->d_in + at, m->obuf, cap - to, s->p.hw_buff_sz, &m->iu, &m->ol, c32, dest + to, &m->sent);
+    } else {
+        if (!*resident) { *resident = true; if (qzd_h2d(s->ctx, s->d_in, src, n) != QZD_OK) return QZ_FAIL; }
+        r = qzd_inflate_stream_to_host(s->ctx, s->d_in + at, n - at, m->obuf, cap - to, s->p.hw_buff_sz, &m->iu, &m->ol, c32, dest + to, &m->sent);
+    }
+    /* Not even the first member fits.  The software path would hand out what fits and keep its inflate state
+     * (src/qatzip_sw.c:342-351, SURVEY 8b "decompress into 1 KB dest"); a segment-parallel decoder has no such state to
+     * keep, so the member is decoded whole into a buffer of its own - size unknown, so grown until it fits - and handed
+     * out piece by piece, this call and the following ones. */
+    uint64_t hcap = std::max<uint64_t>(std::max<uint64_t>(2ull * cap, 8ull * (n - at)), 1u << 20);
+    while (r == QZD_ERR_DSTCAP && to == 0) {
+        hcap = std::min<uint64_t>(hcap, 0xffffffffull);
+        if (!hold_alloc(s, hcap)) break;
+        r = qzd_inflate_stream(s->ctx, s->d_in + at, n - at, s->d_hold, hcap, s->p.hw_buff_sz, &m->iu, &m->ol, gz ? &m->c32 : NULL);
+        if (r == QZD_OK) { m->held = true; m->obuf = s->d_hold; }
+        else hold_release(s);
+        if (hcap >= 0xffffffffull) break;
+        hcap *= 4;
+    }
+    return qz_code(r, QZ_DATA_ERROR);
+}
+
+/* the member's trailer at src + *pos against what was decoded (ol bytes at obuf, CRC-32 c32); *pos moves behind it */
+static int check_trailer(Sess *s, int fmt, const unsigned char *src, uint32_t n, uint32_t *pos, const uint8_t *obuf, uint64_t ol, uint32_t c32)
+{
+    if (fmt == F_GZIP || fmt == F_GZIP_EXT) {
+        if (*pos + 8 > n || rd32(src + *pos) != c32 || rd32(src + *pos + 4) != (uint32_t)ol) return QZ_DATA_ERROR;
+    } else if (fmt == F_ZLIB) {
+        const uint32_t R = 256 * 1024, nr = ol ? (uint32_t)((ol + R - 1) / R) : 1;
+        std::vector<uint32_t> ad(nr);
+        if (*pos + 4 > n || qzd_adler32_chunks(s->ctx, obuf, ol, R, ad.data()) != QZD_OK) return QZ_DATA_ERROR;
+        uint32_t a = 1;
+        for (uint32_t k = 0; k < nr; k++) a = qzd_adler32_combine(a, ad[k], std::min<uint64_t>(R, ol - (uint64_t)k * R));
+        const uint32_t want = (uint32_t)src[*pos] << 24 | (uint32_t)src[*pos + 1] << 16 | (uint32_t)src[*pos + 2] << 8 | src[*pos + 3];
+        if (a != want) return QZ_DATA_ERROR;
+    }
+    *pos += ftr_len(fmt);
+    return QZ_OK;
+}
+
 static int decompress_deflate(QzSession_T *sess, Sess *s, const unsigned char *src, unsigned int *src_len,
                               unsigned char *dest, unsigned int *dest_len, unsigned long *crc)
 {
     const int fmt = s->p.fmt;
     const uint32_t n = *src_len, cap = *dest_len;
     s->out_resident = false;
-    if (s->d_hold) {
-        /* the rest of a member that was larger than the destination (below): the next piece; the member's last input
-         * byte was held back for exactly this, and goes with the last piece */
-        const uint32_t k = (uint32_t)std::min<uint64_t>(cap, s->hold_len - s->hold_pos);
-        if (k == 0 && s->hold_pos < s->hold_len) { *src_len = 0; *dest_len = 0; return QZ_BUF_ERROR; }
-        if (k && qzd_d2h(s->ctx, dest, s->d_hold + s->hold_pos, k) != QZD_OK) return QZ_FAIL;
-        if (crc && k) {
-            uint32_t c = 0;
-            if (qzd_crc32(s->ctx, s->d_hold + s->hold_pos, k, &c) != QZD_OK) return QZ_FAIL;
-            *crc = qzd_crc32_combine((uint32_t)*crc, c, k);
-        }
-        s->hold_pos += k;
-        const bool last_piece = s->hold_pos == s->hold_len && n >= 1;     /* the held-back byte has to be there to be consumed */
-        if (last_piece) { qzd_dev_free(s->ctx, s->d_hold); s->d_hold = NULL; s->hold_len = s->hold_pos = 0; s->end_of_stream = 1; }
-        return deliver(sess, src_len, dest_len, last_piece ? 1 : 0, k, QZ_OK);
-    }
+    if (s->d_hold) return hold_next(sess, s, src_len, dest, dest_len, crc);    /* the rest of a member that was larger than the destination */
     int rc = reserve(s, n, cap);
     if (rc) return rc;
-    /* the source goes to the device when something needs it there: a large member is decoded WHILE it arrives
-     * (qzd_inflate_stream_from_host), everything else after one copy of the whole call */
-    bool resident = false;
+    bool resident = false;                                          /* the call's source is on the device */
     uint32_t ti = 0, to = 0; int ret = QZ_OK;
     bool all_sent = true; uint64_t sent_bytes = 0;                  /* output the device layer has already put into dest */
     s->end_of_stream = 0;
@@ -959,79 +912,26 @@ static int decompress_deflate(QzSession_T *sess, Sess *s, const unsigned char *s
     }
     while (ti < n && to < cap) {                                    /* member loop, src/qatzip_sw.c:415-435 */
         uint32_t es, ed;
-        int hl = parse_header(fmt, src + ti, n - ti, &es, &ed);
+        const int hl = parse_header(fmt, src + ti, n - ti, &es, &ed);
         if (hl < 0) { ret = hl; break; }
-        uint64_t iu = 0, ol = 0; uint32_t c32 = 0;
-        uint8_t *obuf = s->d_out + to;
-        int sent = 0;                                               /* large members reach dest while they are still being decoded */
-        int r;
-        if (!resident && n - ti - hl >= QZ_PIPE_MIN_BYTES) {
-            resident = true;                                        /* (the bytes before this member's payload are never read on the device) */
-            r = qzd_inflate_stream_from_host(s->ctx, src + ti + hl, n - ti - hl, s->d_in + ti + hl, obuf, cap - to, s->p.hw_buff_sz, &iu, &ol,
-                                             (fmt == F_GZIP || fmt == F_GZIP_EXT || crc) ? &c32 : NULL, dest + to, &sent);
-        } else {
-            if (!resident) { resident = true; if (qzd_h2d(s->ctx, s->d_in, src, n) != QZD_OK) { ret = QZ_FAIL; break; } }
-            r = qzd_inflate_stream_to_host(s->ctx, s->d_in + ti + hl, n - ti - hl, obuf, cap - to, s->p.hw_buff_sz, &iu, &ol,
-                                           (fmt == F_GZIP || fmt == F_GZIP_EXT || crc) ? &c32 : NULL, dest + to, &sent);
+        Inflated m;
+        ret = inflate_member(s, src, n, ti + (uint32_t)hl, dest, to, cap, fmt == F_GZIP || fmt == F_GZIP_EXT, crc != NULL, &resident, &m);
+        if (m.sent) sent_bytes += m.ol; else all_sent = false;
+        if (ret != QZ_OK) break;
+        uint32_t pos = ti + (uint32_t)hl + (uint32_t)m.iu;
+        ret = check_trailer(s, fmt, src, n, &pos, m.obuf, m.ol, m.c32);
+        if (ret != QZ_OK) break;
+        if (m.held) {
+            ret = hold_begin(sess, s, m.ol, pos, src_len, dest, dest_len, cap, crc);
+            if (ret == QZ_OK) return ret;
+            break;
         }
-        if (sent) sent_bytes += ol; else all_sent = false;
-        bool held = false;
-        if (r == QZD_ERR_DSTCAP && to == 0) {
-            /* Not even the first member fits.  The software path would hand out what fits and keep its inflate state
-             * (src/qatzip_sw.c:342-351, SURVEY 8b "decompress into 1 KB dest"); a segment-parallel decoder has no
-             * such state to keep, so the member is decoded whole into a buffer of its own - size unknown, so grown
-             * until it fits - and handed out piece by piece, this call and the following ones. */
-            uint64_t hcap = std::max<uint64_t>(std::max<uint64_t>(2ull * cap, 8ull * (n - ti - hl)), 1u << 20);
-            for (;;) {
-                hcap = std::min<uint64_t>(hcap, 0xffffffffull);
-                s->d_hold = (uint8_t *)qzd_dev_alloc(s->ctx, hcap + 4096);
-                if (!s->d_hold) { r = QZD_ERR_DSTCAP; break; }
-                r = qzd_inflate_stream(s->ctx, s->d_in + ti + hl, n - ti - hl, s->d_hold, hcap, s->p.hw_buff_sz, &iu, &ol,
-                                       (fmt == F_GZIP || fmt == F_GZIP_EXT) ? &c32 : NULL);
-                if (r == QZD_OK) { held = true; obuf = s->d_hold; break; }
-                qzd_dev_free(s->ctx, s->d_hold); s->d_hold = NULL;
-                if (r != QZD_ERR_DSTCAP || hcap >= 0xffffffffull) break;
-                hcap *= 4;
-            }
-        }
-        if (r == QZD_ERR_DSTCAP) { ret = QZ_BUF_ERROR; break; }
-        /* only what the DATA is to blame for is a data error: a failed device call is QZ_FAIL, scratch that could not be
-         * had QZ_NOSW_LOW_MEM (there is no software path behind this library to go to) */
-        if (r == QZD_ERR_NOMEM) { ret = QZ_NOSW_LOW_MEM; break; }
-        if (r == QZD_ERR_HIP || r == QZD_ERR_PARAM) { ret = QZ_FAIL; break; }
-        if (r != QZD_OK) { ret = QZ_DATA_ERROR; break; }
-        uint32_t pos = ti + (uint32_t)hl + (uint32_t)iu;
-        if (fmt == F_GZIP || fmt == F_GZIP_EXT) {
-            if (pos + 8 > n || rd32(src + pos) != c32 || rd32(src + pos + 4) != (uint32_t)ol) { ret = QZ_DATA_ERROR; break; }
-            pos += 8;
-        } else if (fmt == F_ZLIB) {
-            const uint32_t R = 256 * 1024, nr = ol ? (uint32_t)((ol + R - 1) / R) : 1;
-            std::vector<uint32_t> ad(nr);
-            if (pos + 4 > n || qzd_adler32_chunks(s->ctx, obuf, ol, R, ad.data()) != QZD_OK) { ret = QZ_DATA_ERROR; break; }
-            uint32_t a = 1;
-            for (uint32_t k = 0; k < nr; k++) a = qzd_adler32_combine(a, ad[k], std::min<uint64_t>(R, ol - (uint64_t)k * R));
-            const uint32_t want = (uint32_t)src[pos] << 24 | (uint32_t)src[pos + 1] << 16 | (uint32_t)src[pos + 2] << 8 | src[pos + 3];
-            if (a != want) { ret = QZ_DATA_ERROR; break; }
-            pos += 4;
-        }
-        if (held) {
-            /* first piece now; everything but the member's last byte counts as consumed, so the caller keeps calling */
-            const uint32_t k = (uint32_t)std::min<uint64_t>(cap, ol);
-            if (k && qzd_d2h(s->ctx, dest, s->d_hold, k) != QZD_OK) { ret = QZ_FAIL; break; }
-            if (crc && k) {
-                uint32_t c = 0;
-                if (qzd_crc32(s->ctx, s->d_hold, k, &c) != QZD_OK) { ret = QZ_FAIL; break; }
-                *crc = *crc == 0 ? c : qzd_crc32_combine((uint32_t)*crc, c, k);
-            }
-            s->hold_len = ol; s->hold_pos = k;
-            return deliver(sess, src_len, dest_len, pos - 1, k, QZ_OK);
-        }
-        if (crc) *crc = (to == 0 && *crc == 0) ? c32 : qzd_crc32_combine((uint32_t)*crc, c32, ol);
-        ti = pos; to += (uint32_t)ol;
+        if (crc) qz_crc_fold_member(crc, to, m.c32, m.ol);
+        ti = pos; to += (uint32_t)m.ol;
         s->end_of_stream = 1;
         if (s->p.stop_at_stream_end) break;
     }
-    if (ret != QZ_OK && s->d_hold) { qzd_dev_free(s->ctx, s->d_hold); s->d_hold = NULL; s->hold_len = s->hold_pos = 0; }
+    if (ret != QZ_OK) hold_release(s);
     /* a later member that is cut short or damaged does not undo the complete ones before it: partial consumption,
      * QZ_OK, and the next call (which starts at that member) reports the error - the member-granular version of what
      * the software path's kept inflate state does ("first half of the stream => QZ_OK, partial output") */
@@ -1055,9 +955,9 @@ static int decompress_direct(QzSession_T *sess, const unsigned char *src, unsign
         if (rc == QZ_OK || rc == QZ_BUF_ERROR) return rc;
         goto fail;
     }
-    if (s->p.fmt == F_LZ4) rc = decompress_lz4(sess, s, src, src_len, dest, dest_len);
+    if (s->p.fmt == F_LZ4) rc = decompress_frames(sess, s, src, src_len, dest, dest_len, lz4_frame_extent, qzd_lz4_decompress_frames, QZ_SHORT_LAST);
     /* qzDecompress2 and the Crc64 calls (may_queue false) answer for a zstd decode session what they do for every LZ4s session */
-    else if (s->p.fmt == F_LZ4S && s->p.zstd_dec && may_queue) rc = decompress_zstd(sess, s, src, src_len, dest, dest_len);
+    else if (s->p.fmt == F_LZ4S && s->p.zstd_dec && may_queue) rc = decompress_frames(sess, s, src, src_len, dest, dest_len, qzd_zd_frame_extent, qzd_zstd_decompress_frames, QZ_SHORT_LAST_UNSIZED);
     else if (s->p.fmt == F_LZ4S) rc = QZ_UNSUPPORTED_FMT;
     else rc = decompress_deflate(sess, s, src, src_len, dest, dest_len, crc);
     sess->thd_sess_stat = rc;
@@ -1406,16 +1306,12 @@ static bool compress_batch(const std::vector<AsyncReq> &run, const std::vector<S
 /* the other direction: a request whose source is exactly one gzip-ext member with its sizes in the header (what
  * qzCompress writes for a last = 1 call, and what the hardware path writes per chunk) can share a launch too - one
  * segment per request, all decoded at once */
-static Sess *batchable_d(const AsyncReq &q, uint32_t *pay, uint32_t *csz, uint32_t *usz)
+static Sess *batchable_d(const AsyncReq &q, QzSized *m)
 {
     Sess *s = NULL;
     if (q.compress || !q.sess || !q.res || ensure_ready(q.sess, &s) < 0 || !s) return NULL;
     if (!(s->p.fmt == F_GZIP_EXT || s->p.fmt == F_GZIP) || q.res->src_len > AQ_BATCH_MAX_REQ) return NULL;
-    uint32_t es = 0, ed = 0;
-    const int hl = parse_header(F_GZIP_EXT, q.src, q.res->src_len, &es, &ed);
-    if (hl < 0 || es == 0 || ed == 0 || (uint64_t)hl + ed + 8 != q.res->src_len || es > q.res->dest_len || es > AQ_BATCH_MAX_REQ) return NULL;
-    *pay = (uint32_t)hl; *csz = ed; *usz = es;
-    return s;
+    return qz_lone_sized_member(q.src, q.res->src_len, q.res->dest_len, AQ_BATCH_MAX_REQ, m) ? s : NULL;
 }
 
 static bool decompress_batch(const std::vector<AsyncReq> &run, const std::vector<Sess *> &ss)
@@ -1425,34 +1321,32 @@ static bool decompress_batch(const std::vector<AsyncReq> &run, const std::vector
     std::vector<qzd_infseg> segs(nm);
     std::vector<qzd_infres> res(nm);
     std::vector<qzd_range> rg(nm);
-    std::vector<uint32_t> c32(nm), pay(nm);
+    std::vector<uint32_t> c32(nm);
+    std::vector<QzSized> mem(nm);
     uint64_t io = 0, oo = 0;
     for (uint32_t i = 0; i < nm; i++) {
-        uint32_t csz = 0, usz = 0;
-        if (!batchable_d(run[i], &pay[i], &csz, &usz)) return false;
-        segs[i].in_off = io; segs[i].in_len = csz; segs[i].out_off = oo; segs[i].out_cap = usz; segs[i].flags = 0; segs[i].pad = csz;
-        rg[i].off = oo; rg[i].len = usz; rg[i].pad = 0;
-        io += (csz + 15u) & ~15u; oo += usz;
+        if (!batchable_d(run[i], &mem[i])) return false;
+        qz_member_seg(&segs[i], &rg[i], io, mem[i].csz, oo, mem[i].usz);
+        io += (mem[i].csz + 15u) & ~15u; oo += mem[i].usz;
     }
     if (reserve(s0, io + 64, oo + 64) != QZ_OK) return false;
     unsigned char *stage = stage_reserve(std::max<uint64_t>(io + 64, oo));
     if (!stage) return false;
-    for (uint32_t i = 0; i < nm; i++) memcpy(stage + segs[i].in_off, run[i].src + pay[i], segs[i].in_len);
+    for (uint32_t i = 0; i < nm; i++) memcpy(stage + segs[i].in_off, run[i].src + mem[i].pay, mem[i].csz);
     if (qzd_h2d(s0->ctx, s0->d_in, stage, io + 64) != QZD_OK) return false;
     if (qzd_inflate_segments(s0->ctx, s0->d_in, s0->d_out, segs.data(), nm, res.data()) != QZD_OK) return false;
     if (qzd_crc32_ranges(s0->ctx, s0->d_out, rg.data(), nm, c32.data()) != QZD_OK) return false;
     if (oo && qzd_d2h(s0->ctx, stage, s0->d_out, oo) != QZD_OK) return false;
     for (uint32_t i = 0; i < nm; i++) {
         QzResult_T *r = run[i].res;
-        const unsigned char *tr = run[i].src + pay[i] + segs[i].in_len;
-        const uint32_t usz = segs[i].out_cap;
-        if (res[i].status != 0 || res[i].out_len != usz || res[i].in_used != segs[i].in_len || rd32(tr) != c32[i] || rd32(tr + 4) != usz) {
+        const uint32_t usz = mem[i].usz;
+        if (!member_ok(res[i], c32[i], run[i].src + mem[i].pay + mem[i].csz, mem[i].csz, usz)) {
             run_sync2(run[i].sess, run[i].src, run[i].dest, r, false, run[i].crcp);      /* the one-call path reports what is wrong with it */
             continue;
         }
         memcpy(run[i].dest, stage + segs[i].out_off, usz);
         unsigned long *crc = req_crc(run[i]);
-        if (crc) *crc = *crc == 0 ? c32[i] : qzd_crc32_combine((uint32_t)*crc, c32[i], usz);
+        if (crc) qz_crc_fold_lone(crc, c32[i], usz);
         r->dest_len = usz; r->ext_rc = 0; r->status = QZ_OK;        /* src_len: the whole member */
         ss[i]->end_of_stream = 1;
         run[i].sess->total_in += r->src_len; run[i].sess->total_out += usz; run[i].sess->thd_sess_stat = QZ_OK;
@@ -1484,9 +1378,9 @@ static void *async_consumer(void *)
         run.push_back(g_aq[g_aq_head++]);
         g_aq_running.assign(1, run[0].sess);
         pthread_mutex_unlock(&g_aq_lock);
-        uint32_t a_ = 0, b_ = 0, c_ = 0;
+        QzSized m_;
         const bool comp = run[0].compress;
-        Sess *s0 = comp ? batchable(run[0]) : batchable_d(run[0], &a_, &b_, &c_);
+        Sess *s0 = comp ? batchable(run[0]) : batchable_d(run[0], &m_);
         if (s0) {
             ss.push_back(s0);
             uint64_t slots = run[0].res->src_len / s0->p.hw_buff_sz + 1;
@@ -1494,7 +1388,7 @@ static void *async_consumer(void *)
             while (g_aq_head < g_aq.size() && slots < AQ_BATCH_MAX_SLOTS && slots * s0->p.hw_buff_sz < AQ_BATCH_MAX_BYTES) {
                 AsyncReq q = g_aq[g_aq_head];
                 pthread_mutex_unlock(&g_aq_lock);                /* ensure_ready may take the global lock */
-                Sess *s = q.compress != comp ? NULL : comp ? batchable(q) : batchable_d(q, &a_, &b_, &c_);
+                Sess *s = q.compress != comp ? NULL : comp ? batchable(q) : batchable_d(q, &m_);
                 /* one launch runs on one GPU: only sessions of the oldest request's device ride along */
                 const bool ok = s && qzd_ctx_device(s->ctx) == qzd_ctx_device(s0->ctx) &&
                                 (!comp || (s->p.fmt == s0->p.fmt && s->p.comp_lvl == s0->p.comp_lvl && s->p.hw_buff_sz == s0->p.hw_buff_sz));
@@ -1602,9 +1496,8 @@ static bool sync_via_queue(QzSession_T *sess, Sess *s, const unsigned char *src,
         if (s->p.comp_lvl < 1 || s->p.comp_lvl > 9) return false;
     } else {
         if (f != F_GZIP_EXT || s->d_hold || s->p.stop_at_stream_end) return false;
-        uint32_t es = 0, ed = 0;
-        const int hl = parse_header(F_GZIP_EXT, src, *src_len, &es, &ed);
-        if (hl < 0 || es == 0 || ed == 0 || (uint64_t)hl + ed + 8 != *src_len || es > *dest_len || es > AQ_BATCH_MAX_REQ) return false;
+        QzSized m;
+        if (!qz_lone_sized_member(src, *src_len, *dest_len, AQ_BATCH_MAX_REQ, &m)) return false;
     }
     QzResult_T r;
     memset(&r, 0, sizeof(r));
@@ -1921,10 +1814,9 @@ extern "C" int qzDecompressWithMetadataExt(QzSession_T *sess, const unsigned cha
         if (qzd_h2d(s->ctx, s->d_in, src, end) != QZD_OK) { rc = QZ_FAIL; goto fail; }
         uint64_t produced = 0;
         const int r = qzd_blocks_decompress(s->ctx, s->d_in, end, recs.data(), nb, B, s->d_out, (uint64_t)nb * B, NULL, &produced);
-        if (r == QZD_ERR_DATA) { rc = QZ_DATA_ERROR; goto fail; }
-        if (r == QZD_ERR_DSTCAP) { rc = QZ_BUF_ERROR; goto fail; }
-        if (r == QZD_ERR_NOMEM) { rc = QZ_NOSW_LOW_MEM; goto fail; }
-        if (r != QZD_OK) { logmsg(LOG_ERROR, "GPU block decompress failed: %s\n", qzd_last_error(s->ctx)); rc = QZ_FAIL; goto fail; }
+        rc = qz_code(r, QZ_FAIL);
+        if (rc == QZ_FAIL) logmsg(LOG_ERROR, "GPU block decompress failed: %s\n", qzd_last_error(s->ctx));
+        if (rc) goto fail;
         if (produced > cap) { rc = QZ_BUF_ERROR; goto fail; }
         if (produced && qzd_d2h(s->ctx, dest, s->d_out, produced) != QZD_OK) { rc = QZ_FAIL; goto fail; }
         sess->thd_sess_stat = QZ_OK;

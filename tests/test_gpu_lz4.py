@@ -106,6 +106,26 @@ def test_api_lz4_session_roundtrip_and_parity():
     s.close()
 
 
+def test_a_content_size_the_blocks_do_not_reach():
+    """An LZ4 session's rule for the segment that may come out short (QZ_SHORT_LAST, qz_unframe.h): the LZ4 kernels do not
+    compare a frame's content size with what its blocks produce, so a frame X whose header claims 100 bytes more than its
+    blocks hold decodes as the LAST frame of a call and fails the call anywhere else - a frame that is not the last has to
+    fill its out_cap for the next one's output to lie behind it.  (liblz4 refuses X wherever it stands; that departure is
+    pinned here, not judged.)  Y is the honest frame built the same way."""
+    import lz4_frame_writer as W
+    x_data, y_data = datagen.gen_bytes("text", 1000, 61), datagen.gen_bytes("text", 1000, 62)
+    X = W.frame([(W.literals_block(x_data), False)], content_size=len(x_data) + 100)
+    Y = W.frame([(W.literals_block(y_data), False)], content_size=len(y_data))
+    s = A.Session(lz4=True)
+    assert s.rc_setup == A.QZ_OK
+    assert s.decompress(Y, 4096) == (A.QZ_OK, len(Y), y_data)
+    assert s.decompress(X, 4096) == (A.QZ_OK, len(X), x_data)
+    assert s.decompress(X + Y, 4096) == (A.QZ_FAIL, 0, b"")
+    assert s.decompress(Y + X, 4096) == (A.QZ_OK, len(Y) + len(X), y_data + x_data)
+    assert s.decompress(X, len(x_data)) == (A.QZ_BUF_ERROR, 0, b"")      # the claimed size is what has to fit
+    s.close()
+
+
 def test_lz4_throughput_smoke(ctx):
     base = datagen.gen("silesia", 32 << 20, 3)
     d_src = ctx.alloc(base.size); d_src.upload(base)
