@@ -285,6 +285,16 @@ int qzd_zstd_compress_frames(qzd_ctx *ctx, const uint8_t *d_src, uint64_t n, uin
  * QZD_ERR_DSTCAP: dst_cap below the bound. */
 int qzd_zstd_encode_frames(qzd_ctx *ctx, const uint8_t *d_literals, const uint32_t *d_seqs, const uint32_t *h_desc,
                            uint32_t nframes, uint8_t *d_dst, uint64_t dst_cap, uint64_t *h_out_len, uint32_t *h_frame_len);
+/* the two calls above with seq_flags, the bits of include/qzamd_zstd_seq.h: 1 - each of the LL, OF and ML tables of a
+ * frame is Predefined, RLE or FSE_Compressed, whichever costs the fewest bits; 2 - offsets are coded against the
+ * repeat-offset history.  0 is the call above, byte for byte.  QZD_ERR_PARAM for a bit above 3; everything else as above.
+ * The sequences, the bound and the frame layout do not change. */
+int qzd_zstd_compress_frames_ex(qzd_ctx *ctx, const uint8_t *d_src, uint64_t n, uint32_t block_sz, uint32_t mini_match,
+                                int level, uint8_t *d_dst, uint64_t dst_cap, uint64_t *h_out_len, uint32_t *h_frame_len,
+                                uint32_t seq_flags);
+int qzd_zstd_encode_frames_ex(qzd_ctx *ctx, const uint8_t *d_literals, const uint32_t *d_seqs, const uint32_t *h_desc,
+                              uint32_t nframes, uint8_t *d_dst, uint64_t dst_cap, uint64_t *h_out_len, uint32_t *h_frame_len,
+                              uint32_t seq_flags);
 /* decode nsegs frames (any block mode; block checksums and the content checksum verified on the GPU); replaces
  * LZ4F_decompress, src/qatzip_sw.c:496, and answers as it does: a wrong block checksum is a data error whether or not the
  * frame has a content checksum, and in a frame of independent blocks (FLG bit 5) a match that reaches in front of its own

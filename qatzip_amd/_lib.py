@@ -76,6 +76,8 @@ def load(build_if_missing=True):
     L.qzd_zstd_bound.argtypes = [C.c_uint64, C.c_uint32]; L.qzd_zstd_bound.restype = C.c_uint64
     L.qzd_zstd_compress_frames.argtypes = L.qzd_lz4s_compress_blocks.argtypes
     L.qzd_zstd_encode_frames.argtypes = [vp, u8p, vp, vp, C.c_uint32, u8p, C.c_uint64, C.POINTER(C.c_uint64), vp]
+    L.qzd_zstd_compress_frames_ex.argtypes = L.qzd_zstd_compress_frames.argtypes + [C.c_uint32]
+    L.qzd_zstd_encode_frames_ex.argtypes = L.qzd_zstd_encode_frames.argtypes + [C.c_uint32]
     L.qzd_zstd_decompress_frames.argtypes = [vp, u8p, u8p, vp, C.c_uint32, vp]
     L.qzd_chunk_lens.argtypes = [vp, vp, C.c_uint32]
     L.qzd_shard_root_create.argtypes = [vp, C.c_uint32, C.c_uint64, C.c_char_p, C.POINTER(vp)]
@@ -127,6 +129,7 @@ def exported_symbols():
             "qzd_lz4hc_compress_frames", "qzd_lz4hc_compress_frames_hw", "qzd_lz4hc_compress_linked",
             "qzd_lz4s_bound", "qzd_lz4s_compress_blocks",
             "qzd_zstd_bound", "qzd_zstd_compress_frames", "qzd_zstd_encode_frames", "qzd_zstd_decompress_frames",
+            "qzd_zstd_compress_frames_ex", "qzd_zstd_encode_frames_ex",
             "qzd_crcn_ranges", "qzd_xxh32_ranges", "qzd_blocks_compress", "qzd_blocks_decompress",
             "qzd_crc32_fold", "qzd_pcie_peak", "qzd_rccl_unique_id", "qzd_rccl_create", "qzd_rccl_gather", "qzd_rccl_close"]
 
@@ -331,25 +334,28 @@ class Context:
                                                   d_dst.nbytes if dst_cap is None else dst_cap, C.byref(ol), lens.ctypes.data))
         return ol.value, lens[:nb]
 
-    def zstd_compress_frames(self, d_src, n, d_dst, block_sz=65536, mini_match=3, level=1, dst_cap=None):
-        """every block_sz bytes one zstd frame (the LZ4s parse, entropy-coded on the device) -> (out_len, per-frame lengths)"""
+    def zstd_compress_frames(self, d_src, n, d_dst, block_sz=65536, mini_match=3, level=1, dst_cap=None, seq_flags=None):
+        """every block_sz bytes one zstd frame (the LZ4s parse, entropy-coded on the device) -> (out_len, per-frame lengths).
+        seq_flags (the bits of include/qzamd_zstd_seq.h): through qzd_zstd_compress_frames_ex"""
         nb = (n + block_sz - 1) // block_sz
         ol = C.c_uint64(0)
         lens = np.zeros(max(nb, 1), np.uint32)
-        self._chk(self.L.qzd_zstd_compress_frames(self.h, d_src.ptr, n, block_sz, mini_match, level, d_dst.ptr,
-                                                  d_dst.nbytes if dst_cap is None else dst_cap, C.byref(ol), lens.ctypes.data))
+        args = (self.h, d_src.ptr, n, block_sz, mini_match, level, d_dst.ptr, d_dst.nbytes if dst_cap is None else dst_cap,
+                C.byref(ol), lens.ctypes.data)
+        self._chk(self.L.qzd_zstd_compress_frames(*args) if seq_flags is None else self.L.qzd_zstd_compress_frames_ex(*args, seq_flags))
         return ol.value, lens[:nb]
 
-    def zstd_encode_frames(self, d_literals, d_seqs, desc, d_dst, dst_cap=None):
+    def zstd_encode_frames(self, d_literals, d_seqs, desc, d_dst, dst_cap=None, seq_flags=None):
         """the entropy stage alone: desc = uint32 x 3 per frame (content size, records, literals), d_seqs the records (uint32 x
         3: literal length, match length, offset), d_literals their literals -> (rc, out_len, per-frame lengths); rc is the
-        device layer's (QZD_ERR_PARAM -1, QZD_ERR_DATA -4 for what it refuses)"""
+        device layer's (QZD_ERR_PARAM -1, QZD_ERR_DATA -4 for what it refuses).  seq_flags: through qzd_zstd_encode_frames_ex"""
         desc = np.ascontiguousarray(desc, dtype=np.uint32)
         nf = len(desc) // 3
         ol = C.c_uint64(0)
         lens = np.zeros(max(nf, 1), np.uint32)
-        rc = self.L.qzd_zstd_encode_frames(self.h, d_literals.ptr, d_seqs.ptr, desc.ctypes.data, nf, d_dst.ptr,
-                                           d_dst.nbytes if dst_cap is None else dst_cap, C.byref(ol), lens.ctypes.data)
+        args = (self.h, d_literals.ptr, d_seqs.ptr, desc.ctypes.data, nf, d_dst.ptr, d_dst.nbytes if dst_cap is None else dst_cap,
+                C.byref(ol), lens.ctypes.data)
+        rc = self.L.qzd_zstd_encode_frames(*args) if seq_flags is None else self.L.qzd_zstd_encode_frames_ex(*args, seq_flags)
         return rc, ol.value, lens[:nf]
 
     LZ4D_ROUTES = {"auto": 0, "wave": 1, "blocks": 2}

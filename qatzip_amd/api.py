@@ -141,6 +141,7 @@ def lib():
         L.qzSetSessionCrc64Config.argtypes = [P(QzSession), P(QzCrc64Config)]
         L.qzGetSessionCrc32Config.argtypes = [P(QzSession), P(QzCrc32Config)]
         L.qzSetSessionCrc32Config.argtypes = [P(QzSession), P(QzCrc32Config)]
+        L.qzSetSessionZstdSeqAMD.argtypes = [P(QzSession), C.c_uint]
         _bound = True
     return L
 
@@ -179,6 +180,9 @@ class Metadata:
         rc = self.L.qzFreeMetadata(self.h) if self.h else QZ_PARAMS
         self.h = C.c_void_p()
         return rc
+
+
+QZ_ZSTD_SEQ_FSE_TABLES, QZ_ZSTD_SEQ_REPEAT_OFFSETS = 1, 2      # include/qzamd_zstd_seq.h
 
 
 class Session:
@@ -284,6 +288,10 @@ class Session:
     def set_crc64(self, polynomial, initial_value, reflect_in, reflect_out, xor_out):
         g = QzCrc64Config(polynomial, initial_value, reflect_in, reflect_out, xor_out)
         return self.L.qzSetSessionCrc64Config(C.byref(self.s), C.byref(g))
+
+    def set_zstd_seq(self, flags):
+        """qzSetSessionZstdSeqAMD (include/qzamd_zstd_seq.h): QZ_ZSTD_SEQ_FSE_TABLES | QZ_ZSTD_SEQ_REPEAT_OFFSETS, 0 for neither"""
+        return self.L.qzSetSessionZstdSeqAMD(C.byref(self.s), flags)
 
     def set_crc32(self, polynomial, initial_value, reflect_in, reflect_out, xor_out):
         g = QzCrc32Config(polynomial, initial_value, reflect_in, reflect_out, xor_out)

@@ -18,6 +18,7 @@ def _sources():
     out.append(os.path.join(os.path.dirname(HERE), "include", "qzamd_device.h"))
     out.append(os.path.join(os.path.dirname(HERE), "include", "qzamd_zstd.h"))
     out.append(os.path.join(os.path.dirname(HERE), "include", "qzamd_zstd_dec.h"))
+    out.append(os.path.join(os.path.dirname(HERE), "include", "qzamd_zstd_seq.h"))
     q = os.path.join(os.path.dirname(HERE), "include", "qatzip.h")
     if os.path.exists(q):
         out.append(q)

@@ -17,6 +17,7 @@
 #include "qatzip.h"
 #include "qzamd_zstd.h"
 #include "qzamd_zstd_dec.h"
+#include "qzamd_zstd_seq.h"
 #include "../csrc/qzd_zstdd_host.h"
 
 #define PIECE_BYTES (64u * 1024 * 1024)
@@ -31,6 +32,9 @@ static void usage(FILE *f)
                "  -m <3|4>     lz4s_mini_match (default 3)\n"
                "  -o <name>    write to <name> instead of <file>.zst\n"
                "  -k           keep <file>\n"
+               "  --seq-tables the sequence tables of a frame Predefined, RLE or FSE_Compressed, whichever is smallest\n"
+               "  --repeat-offsets\n"
+               "               offsets coded against the repeat-offset history\n"
                "  -d           not offered under this spelling (exit 2): use --decompress, or zstd -d\n"
                "  --decompress <file.zst>\n"
                "               decode <file.zst> (zstd and skippable frames of any writer, no dictionaries) to <file>,\n"
@@ -114,10 +118,14 @@ int main(int argc, char **argv)
     unsigned hw = 65536, level = 1, mm = 3;
     const char *oname = NULL;
     int keep = 0, c, decompress = 0;
-    static const struct option longopts[] = { { "decompress", no_argument, NULL, 'D' }, { NULL, 0, NULL, 0 } };
+    unsigned seq_flags = 0;
+    static const struct option longopts[] = { { "decompress", no_argument, NULL, 'D' }, { "seq-tables", no_argument, NULL, 'T' },
+                                              { "repeat-offsets", no_argument, NULL, 'R' }, { NULL, 0, NULL, 0 } };
     while ((c = getopt_long(argc, argv, "C:L:m:o:kdh", longopts, NULL)) != -1) {
         switch (c) {
         case 'D': decompress = 1; break;
+        case 'T': seq_flags |= QZ_ZSTD_SEQ_FSE_TABLES; break;
+        case 'R': seq_flags |= QZ_ZSTD_SEQ_REPEAT_OFFSETS; break;
         case 'C': hw = (unsigned)strtoul(optarg, NULL, 0); break;
         case 'L': level = (unsigned)strtoul(optarg, NULL, 0); break;
         case 'm': mm = (unsigned)strtoul(optarg, NULL, 0); break;
@@ -180,6 +188,7 @@ int main(int argc, char **argv)
     p.qzCallback = NULL; p.qzCallback_external = NULL;
     rc = qzSetupSessionZstdAMD(&sess, &p);
     if (rc != QZ_OK) { fprintf(stderr, "qzstd-amd: these parameters are refused (%d): -C a power of two in 1024 .. 131072, -L 1-12, -m 3 or 4\n", rc); return 2; }
+    if (seq_flags && qzSetSessionZstdSeqAMD(&sess, seq_flags) != QZ_OK) { fprintf(stderr, "qzstd-amd: the sequence options are refused\n"); qzTeardownSession(&sess); return 2; }
 
     int status = 1, created = 0;
     FILE *in = fopen(iname, "rb"), *out = NULL;

@@ -34,6 +34,7 @@
 #include "../../include/qzamd_device.h"
 #include "../../include/qzamd_zstd.h"
 #include "../../include/qzamd_zstd_dec.h"
+#include "../../include/qzamd_zstd_seq.h"
 #include "qzd_zstdd_host.h"             /* a zstd frame's extent */
 #include "qz_frame.h"                   /* the F_* formats, bounds, the delivery rule, member framing, the crc folds */
 #include "qz_unframe.h"                 /* ... and of the decompress calls: member headers, sized members, frame plans, the crc folds */
@@ -45,6 +46,7 @@ struct Params {
     unsigned char stop_at_stream_end, zlib_format; qzLZ4SCallbackFn cb; void *cb_ext; unsigned lz4s_mini_match;
     bool zstd;                      /* an F_LZ4S session made by qzSetupSessionZstdAMD: the same parse, written as zstd frames */
     bool zstd_dec;                  /* ... made by qzSetupSessionZstdDecAMD: qzDecompress reads zstd frames */
+    unsigned zstd_seq;              /* ... how its frames' sequences are coded: the flags of qzSetSessionZstdSeqAMD, 0 at setup */
 };
 
 struct Sess {
@@ -159,7 +161,7 @@ static int lz4s_to(Params &p, const QzSessionParamsLZ4S_T *s)
     if (s->lz4s_mini_match < 3 || s->lz4s_mini_match > 4) return QZ_PARAMS;
     p = g_def;
     from_common(p, s->common_params);
-    p.fmt = F_LZ4S; p.zstd = false; p.zstd_dec = false;
+    p.fmt = F_LZ4S; p.zstd = false; p.zstd_dec = false; p.zstd_seq = 0;
     p.cb = s->qzCallback; p.cb_ext = s->qzCallback_external; p.lz4s_mini_match = s->lz4s_mini_match;
     return check_common(p, true);
 }
@@ -358,6 +360,16 @@ extern "C" int qzSetupSessionZstdDecAMD(QzSession_T *sess, QzSessionParamsLZ4S_T
     if (p.hw_buff_sz > 128 * 1024 || p.cb) return QZ_PARAMS;
     p.direction = dir; p.zstd = true; p.zstd_dec = true;
     return make_session(sess, p);
+}
+
+/* how a zstd session that compresses codes its sequences (include/qzamd_zstd_seq.h); the next qzCompress* call sees it */
+extern "C" int qzSetSessionZstdSeqAMD(QzSession_T *sess, unsigned int flags)
+{
+    Sess *s = sess ? (Sess *)sess->internal : NULL;
+    if (!s || s->p.fmt != F_LZ4S || !s->p.zstd || (s->p.zstd_dec && s->p.direction != QZ_DIR_BOTH)) return QZ_PARAMS;
+    if (flags & ~(QZ_ZSTD_SEQ_FSE_TABLES | QZ_ZSTD_SEQ_REPEAT_OFFSETS)) return QZ_PARAMS;
+    s->p.zstd_seq = flags;
+    return QZ_OK;
 }
 
 static void async_drain(QzSession_T *sess);   /* queued qzCompress2/qzDecompress2 requests of a session finish first */
@@ -622,8 +634,10 @@ static int compress_lz4s(QzSession_T *sess, Sess *s, const unsigned char *src, u
     std::vector<uint32_t> lens(nchunks);
     uint64_t produced = 0;
     /* a zstd session: the same chunks, the same parse, a frame each instead of a block */
-    if ((s->p.zstd ? qzd_zstd_compress_frames : qzd_lz4s_compress_blocks)(s->ctx, s->d_in, n, hw, s->p.lz4s_mini_match, (int)s->p.comp_lvl,
-                                                                          s->d_out, s->out_cap, &produced, lens.data()) != QZD_OK) {
+    if ((s->p.zstd ? qzd_zstd_compress_frames_ex(s->ctx, s->d_in, n, hw, s->p.lz4s_mini_match, (int)s->p.comp_lvl, s->d_out, s->out_cap,
+                                                 &produced, lens.data(), s->p.zstd_seq)
+                   : qzd_lz4s_compress_blocks(s->ctx, s->d_in, n, hw, s->p.lz4s_mini_match, (int)s->p.comp_lvl, s->d_out, s->out_cap,
+                                              &produced, lens.data())) != QZD_OK) {
         logmsg(LOG_ERROR, "GPU %s failed: %s\n", s->p.zstd ? "zstd" : "LZ4s", qzd_last_error(s->ctx));
         return QZ_FAIL;
     }

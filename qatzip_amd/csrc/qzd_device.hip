@@ -1311,14 +1311,16 @@ extern "C" int qzd_lz4s_compress_blocks(qzd_ctx *c, const uint8_t *d_src, uint64
 /* per chunk of c bytes 4 + 1 + 4 + 3 + c: a block that would not be smaller than the chunk is written Raw */
 extern "C" uint64_t qzd_zstd_bound(uint64_t n, uint32_t block_sz) { return qzd_zs_bound(n, block_sz); }
 
-extern "C" int qzd_zstd_compress_frames(qzd_ctx *c, const uint8_t *d_src, uint64_t n, uint32_t block_sz, uint32_t mini_match,
-                                        int level, uint8_t *d_dst, uint64_t dst_cap, uint64_t *h_out_len, uint32_t *h_frame_len)
+extern "C" int qzd_zstd_compress_frames_ex(qzd_ctx *c, const uint8_t *d_src, uint64_t n, uint32_t block_sz, uint32_t mini_match,
+                                           int level, uint8_t *d_dst, uint64_t dst_cap, uint64_t *h_out_len, uint32_t *h_frame_len,
+                                           uint32_t seq_flags)
 {
     if (!c || !d_dst || (n && !d_src) || !h_out_len) return QZD_ERR_PARAM;
     if (!qzd_zs_params_ok(block_sz, mini_match)) {
         snprintf(c->err, sizeof(c->err), "zstd: mini_match 3 or 4, block_sz a power of two in 1 KB .. 128 KB");
         return QZD_ERR_PARAM;
     }
+    if (!qzd_zs_seq_flags_ok(seq_flags)) { snprintf(c->err, sizeof(c->err), "zstd: seq_flags has the bits 1 and 2"); return QZD_ERR_PARAM; }
     if (level < 1 || level > 12) { snprintf(c->err, sizeof(c->err), "zstd: levels 1-12 (level %d asked for)", level); return QZD_ERR_UNSUPPORTED; }
     if ((n + block_sz - 1) / block_sz > 0x7fffffffull) { snprintf(c->err, sizeof(c->err), "zstd: too many frames"); return QZD_ERR_UNSUPPORTED; }
     if (dst_cap < qzd_zs_bound(n, block_sz)) { snprintf(c->err, sizeof(c->err), "destination too small"); return QZD_ERR_DSTCAP; }
@@ -1335,16 +1337,28 @@ extern "C" int qzd_zstd_compress_frames(qzd_ctx *c, const uint8_t *d_src, uint64
     return slot_rounds(c, nb, stride, batch, d_dst, dst_cap, h_out_len, h_frame_len, [&](uint32_t b, uint32_t bn, uint8_t *slots) -> int {
         const uint64_t boff = (uint64_t)b * block_sz;
         HIPCHK(c, hipMemsetAsync(c->k1_counter, 0, 4, st));
-        hipLaunchKernelGGL(qzk_zstd_pull_kernel, dim3(std::min<uint32_t>(bn, waves)), dim3(64), 0, st, d_src + boff, n - boff,
-                           block_sz, bn, slots, stride, c->d_len + b, mini_match, c->k1_counter, c->d_lane);
+        if (seq_flags)
+            hipLaunchKernelGGL(qzk_zstd_pull_seq_kernel, dim3(std::min<uint32_t>(bn, waves)), dim3(64), 0, st, d_src + boff, n - boff,
+                               block_sz, bn, slots, stride, c->d_len + b, mini_match, c->k1_counter, c->d_lane, seq_flags);
+        else
+            hipLaunchKernelGGL(qzk_zstd_pull_kernel, dim3(std::min<uint32_t>(bn, waves)), dim3(64), 0, st, d_src + boff, n - boff,
+                               block_sz, bn, slots, stride, c->d_len + b, mini_match, c->k1_counter, c->d_lane);
         return QZD_OK;
     });
 }
 
-extern "C" int qzd_zstd_encode_frames(qzd_ctx *c, const uint8_t *d_literals, const uint32_t *d_seqs, const uint32_t *h_desc,
-                                      uint32_t nframes, uint8_t *d_dst, uint64_t dst_cap, uint64_t *h_out_len, uint32_t *h_frame_len)
+extern "C" int qzd_zstd_compress_frames(qzd_ctx *c, const uint8_t *d_src, uint64_t n, uint32_t block_sz, uint32_t mini_match,
+                                        int level, uint8_t *d_dst, uint64_t dst_cap, uint64_t *h_out_len, uint32_t *h_frame_len)
+{
+    return qzd_zstd_compress_frames_ex(c, d_src, n, block_sz, mini_match, level, d_dst, dst_cap, h_out_len, h_frame_len, 0);
+}
+
+extern "C" int qzd_zstd_encode_frames_ex(qzd_ctx *c, const uint8_t *d_literals, const uint32_t *d_seqs, const uint32_t *h_desc,
+                                         uint32_t nframes, uint8_t *d_dst, uint64_t dst_cap, uint64_t *h_out_len, uint32_t *h_frame_len,
+                                         uint32_t seq_flags)
 {
     if (!c || !d_dst || !h_out_len || (nframes && (!h_desc || !d_literals || !d_seqs))) return QZD_ERR_PARAM;
+    if (!qzd_zs_seq_flags_ok(seq_flags)) { snprintf(c->err, sizeof(c->err), "zstd: seq_flags has the bits 1 and 2"); return QZD_ERR_PARAM; }
     *h_out_len = 0;
     if (!nframes) return QZD_OK;
     if (nframes > 0x7fffffffu / 2) { snprintf(c->err, sizeof(c->err), "zstd: too many frames"); return QZD_ERR_UNSUPPORTED; }
@@ -1359,22 +1373,31 @@ extern "C" int qzd_zstd_encode_frames(qzd_ctx *c, const uint8_t *d_literals, con
     if (dst_cap < bound) { snprintf(c->err, sizeof(c->err), "destination too small"); return QZD_ERR_DSTCAP; }
     hipSetDevice(c->device);
     const uint32_t stride = qzd_zs_stride(maxc);
-    /* d_lane: the descriptions, then the word a wave sets when it meets records that are not a frame's */
+    const uint32_t cus = c->cus ? c->cus : 256u;
+    const uint32_t batch = qzd_slot_batch(nframes, stride, QZD_SLOT_GIGABYTE), waves = std::min<uint32_t>(batch, QZD_ZS_WPC * cus);
+    /* d_lane: the descriptions, then the word a wave sets when it meets records that are not a frame's, then (seq_flags) per
+     * wave the offset values of the frame it codes */
     const size_t descb = ((size_t)nframes * sizeof(qzk_zs_fdesc) + 15) & ~(size_t)15;
-    QZD_TRY(grow_dev(c, (void **)&c->d_lane, &c->lane_cap, descb + 16));
+    const uint32_t ofv_words = seq_flags ? qzd_zs_ofv_words(fd.data(), nframes) : 0;
+    QZD_TRY(grow_dev(c, (void **)&c->d_lane, &c->lane_cap, descb + 16 + (size_t)waves * ofv_words * 4));
     qzk_zs_fdesc *d_fd = (qzk_zs_fdesc *)c->d_lane;
     uint32_t *d_bad = (uint32_t *)(c->d_lane + descb);
+    uint32_t *d_ofv = (uint32_t *)(c->d_lane + descb + 16);
     hipStream_t st = c->st[0];
-    const uint32_t cus = c->cus ? c->cus : 256u;
     uint32_t bad = 0;
-    QZD_TRY(slot_rounds(c, nframes, stride, qzd_slot_batch(nframes, stride, QZD_SLOT_GIGABYTE), d_dst, dst_cap, h_out_len, NULL, [&](uint32_t b, uint32_t bn, uint8_t *slots) -> int {
+    QZD_TRY(slot_rounds(c, nframes, stride, batch, d_dst, dst_cap, h_out_len, NULL, [&](uint32_t b, uint32_t bn, uint8_t *slots) -> int {
         if (b == 0) {                                               /* the call's first launches: the descriptions, the word cleared */
             HIPCHK(c, hipMemcpyAsync(d_fd, fd.data(), (size_t)nframes * sizeof(qzk_zs_fdesc), hipMemcpyHostToDevice, st));
             HIPCHK(c, hipMemsetAsync(d_bad, 0, 4, st));
         }
         HIPCHK(c, hipMemsetAsync(c->k1_counter, 0, 4, st));
-        hipLaunchKernelGGL(qzk_zstd_encode_kernel, dim3(std::min<uint32_t>(bn, QZD_ZS_WPC * cus)), dim3(64), 0, st, d_literals,
-                           (const qzk_zs_seq *)d_seqs, d_fd + b, bn, slots, stride, c->d_len + b, d_bad, c->k1_counter);
+        if (seq_flags)
+            hipLaunchKernelGGL(qzk_zstd_encode_seq_kernel, dim3(std::min<uint32_t>(bn, waves)), dim3(64), 0, st, d_literals,
+                               (const qzk_zs_seq *)d_seqs, d_fd + b, bn, slots, stride, c->d_len + b, d_bad, c->k1_counter, d_ofv, ofv_words,
+                               seq_flags);
+        else
+            hipLaunchKernelGGL(qzk_zstd_encode_kernel, dim3(std::min<uint32_t>(bn, waves)), dim3(64), 0, st, d_literals,
+                               (const qzk_zs_seq *)d_seqs, d_fd + b, bn, slots, stride, c->d_len + b, d_bad, c->k1_counter);
         return QZD_OK;
     }, [&]() -> int {                                               /* fd and bad outlive the copies: the driver waits for st */
         HIPCHK(c, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st));
@@ -1387,6 +1410,12 @@ extern "C" int qzd_zstd_encode_frames(qzd_ctx *c, const uint8_t *d_literals, con
     }
     if (h_frame_len) HIPCHK(c, hipMemcpy(h_frame_len, c->d_len, (size_t)nframes * 4, hipMemcpyDeviceToHost));      /* only of frames that are good */
     return QZD_OK;
+}
+
+extern "C" int qzd_zstd_encode_frames(qzd_ctx *c, const uint8_t *d_literals, const uint32_t *d_seqs, const uint32_t *h_desc,
+                                      uint32_t nframes, uint8_t *d_dst, uint64_t dst_cap, uint64_t *h_out_len, uint32_t *h_frame_len)
+{
+    return qzd_zstd_encode_frames_ex(c, d_literals, d_seqs, h_desc, nframes, d_dst, dst_cap, h_out_len, h_frame_len, 0);
 }
 
 /* 0 auto, 1 every frame on one wave (qzk_lz4d_kernel), 2 a wave per block for every candidate frame that qualifies */

@@ -44,6 +44,17 @@ static inline bool qzd_zs_describe(const uint32_t *h_desc, uint32_t nframes, qzk
     return true;
 }
 
+/* seq_flags of the _ex calls: the two bits of include/qzamd_zstd_seq.h */
+static inline bool qzd_zs_seq_flags_ok(uint32_t flags) { return flags <= (QZK_ZS_SEQ_FSE | QZK_ZS_SEQ_REP); }
+
+/* the words of offset values a wave of qzk_zstd_encode_seq_kernel needs: the records of the longest frame */
+static inline uint32_t qzd_zs_ofv_words(const qzk_zs_fdesc *fd, uint32_t nframes)
+{
+    uint32_t m = 1;
+    for (uint32_t i = 0; i < nframes; i++) if (fd[i].nseq > m) m = fd[i].nseq;
+    return (m + 3u) & ~3u;
+}
+
 /* offs[i] = where frame i begins; returns the total */
 static inline uint64_t qzd_zs_scan(const uint32_t *lens, uint32_t n, uint64_t *offs)
 {

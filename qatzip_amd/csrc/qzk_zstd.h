@@ -12,8 +12,19 @@
  *   sequences:= count in 1, 2 or 3 bytes | modes | per RLE table its code | the backward bitstream.  Each of LL, OF, ML is
  *               RLE_Mode when every sequence has the same code and Predefined_Mode otherwise.  The offset value is always
  *               offset + 3: no repeat offsets.
+ *   sequences, with seq_flags (qzamd_zstd_seq.h; the _seq kernels, qzk_zs_sequences_x):
+ *               count | modes | per table in LL, OF, ML order nothing, its one code, or its description | the bitstream.
+ *               QZK_ZS_SEQ_REP: the offset value comes from the repeat-offset history (RFC 8878, 3.1.1.5), 1, 4, 8 at the
+ *               frame's start: with a literal length above 0, rep1 / rep2 / rep3 are 1 / 2 / 3; with a literal length of 0,
+ *               rep2 / rep3 / rep1 - 1 are 1 / 2 / 3 and an offset equal to rep1 is offset + 3; the lowest value that fits.
+ *               QZK_ZS_SEQ_FSE: a table that is not RLE is Predefined or FSE_Compressed, whichever takes fewer bits by an
+ *               exact count (state bits of the whole chain, the final state, the description's bytes), Predefined on a
+ *               tie.  Accuracy: log2(ns - 1) - 2 kept in 5 .. 9 (offsets 5 .. 8), and at least log2 of the codes present,
+ *               rounded up.  Counts: count * 2^accuracy / ns rounded to nearest, at least 1 for a code that occurs; what
+ *               the sum lacks goes to the most frequent code, what it has too much is taken from the then most frequent
+ *               one at a time, the lower code among equals; no "less than one" entries.
  *
- * Not written: FSE_Compressed and Repeat modes, treeless literals, more than one block, dictionaries, checksums.
+ * Not written: Repeat_Mode tables, treeless literals, more than one block, dictionaries, checksums.
  *
  * The record emitter follows decLz4Block's rule: the literals of an M == 0 sequence join the next sequence (so a literal
  * length can pass 65535: LL code 35), a match cut into pieces gives one record per piece, and the literals a chunk ends with
@@ -44,6 +55,10 @@
  *
  * LDS: the stage's working set (qzk_zs_lds, 7.5 KiB) lies over the parse's table, which is dead by then; the three predefined
  * tables (qzk_zs_tabs, 1.7 KiB) are built once per wave and live beside it: 17.7 KiB a wave, nine waves a CU (K4s: ten).
+ * With seq_flags a chunk's own tables and the stage's further scratch (qzk_zs_xlds, 6.5 KiB) lie behind qzk_zs_lds in the
+ * same 16 KiB: the wave's LDS does not grow.  The stage then runs five passes over the records: offset values (the history
+ * is serial: a trip of 64 records in the lanes' registers, read one by one), the three histograms by LDS atomics, a table plan per lane
+ * 0-2, the cost walk (lanes 0-2 in the chunk's tables, 3-5 in the predefined ones), and the bitstream as above.
  */
 #ifndef QZK_ZSTD_H
 #define QZK_ZSTD_H
@@ -108,9 +123,11 @@ QZ_DEV void qzk_l4s_emit_tail(qzk_zs_rec &e, const uint8_t *lit, uint32_t L, int
 
 /* ------------------------------------------------------------------ FSE encoding tables */
 /* a state is kept as table size + index.  Coding symbol s from state x: nb = (x + dnb[s]) >> 16 low bits of x go out,
- * the next state is st[(x >> nb) + dfs[s]].  Serial: run by one lane.  cnt: nsym bytes of scratch, spread: 1 << log. */
-QZ_DEV void qzk_zs_fse_build(const int8_t *norm, uint32_t nsym, uint32_t log, uint16_t *st, uint32_t *dnb, int32_t *dfs,
-                             uint8_t *spread, uint8_t *cnt)
+ * the next state is st[(x >> nb) + dfs[s]].  Serial: run by one lane.  cnt: nsym entries of scratch, spread: 1 << log.
+ * N and C hold a count and a position of the table: int8_t and uint8_t up to accuracy 6, int16_t and uint16_t above. */
+template <typename N, typename C>
+QZ_DEV void qzk_zs_fse_build(const N *norm, uint32_t nsym, uint32_t log, uint16_t *st, uint32_t *dnb, int32_t *dfs,
+                             uint8_t *spread, C *cnt)
 {
     const uint32_t size = 1u << log, mask = size - 1, step = (size >> 1) + (size >> 3) + 3;
     uint32_t high = size - 1, pos = 0, total = 0;
@@ -122,7 +139,7 @@ QZ_DEV void qzk_zs_fse_build(const int8_t *norm, uint32_t nsym, uint32_t log, ui
         }
     for (uint32_t s = 0; s < nsym; s++) {
         const int n = norm[s];
-        cnt[s] = (uint8_t)total;                                    /* where the symbol's states begin in st */
+        cnt[s] = (C)total;                                          /* where the symbol's states begin in st */
         if (n == 0) { dnb[s] = ((log + 1) << 16) - size; dfs[s] = 0; }
         else if (n == -1 || n == 1) { dnb[s] = (log << 16) - size; dfs[s] = (int32_t)total - 1; total++; }
         else {
@@ -462,16 +479,17 @@ QZ_DEV uint32_t qzk_zs_literals(qzk_zs_lds *S, const uint8_t *lits, uint32_t nl,
 /* ------------------------------------------------------------------ sequences */
 /* the codes and extra bits of one record */
 typedef struct { uint32_t llc, ofc, mlc, llx, ofx, mlx; } qzk_zs_codes;
-QZ_DEV qzk_zs_codes qzk_zs_code(const qzk_zs_seq q)
+QZ_DEV qzk_zs_codes qzk_zs_code_v(uint32_t ll, uint32_t ml, uint32_t ov)       /* ov: the offset value, 1 .. 3 a repeat code */
 {
     qzk_zs_codes c;
-    const uint32_t mlb = q.ml - 3, ov = q.off + 3;
-    c.llc = qzk_zs_ll_code(q.ll); c.mlc = qzk_zs_ml_code(mlb); c.ofc = qzk_zs_hb(ov);
-    c.llx = q.ll & ((1u << QZK_ZS_LL_BITS[c.llc]) - 1);
+    const uint32_t mlb = ml - 3;
+    c.llc = qzk_zs_ll_code(ll); c.mlc = qzk_zs_ml_code(mlb); c.ofc = qzk_zs_hb(ov);
+    c.llx = ll & ((1u << QZK_ZS_LL_BITS[c.llc]) - 1);
     c.mlx = mlb & ((1u << QZK_ZS_ML_BITS[c.mlc]) - 1);
     c.ofx = ov & ((1u << c.ofc) - 1);
     return c;
 }
+QZ_DEV qzk_zs_codes qzk_zs_code(const qzk_zs_seq q) { return qzk_zs_code_v(q.ll, q.ml, q.off + 3); }
 
 /* the sequences section of seqs[0..ns) at out, where `cap` bytes may be stored; returns its size, QZK_ZS_OVER when it does
  * not fit.  Records as qzk_zs_check leaves them: ml >= 3, 1 <= off, all at most 128 KB. */
@@ -555,6 +573,263 @@ QZ_DEV uint32_t qzk_zs_sequences(qzk_zs_lds *S, const qzk_zs_tabs *T, const qzk_
     return w.over ? QZK_ZS_OVER : op + w.op;
 }
 
+/* ------------------------------------------------------------------ sequences, with chosen tables and repeat offsets */
+#define QZK_ZS_SEQ_FSE 1u           /* QZ_ZSTD_SEQ_FSE_TABLES */
+#define QZK_ZS_SEQ_REP 2u           /* QZ_ZSTD_SEQ_REPEAT_OFFSETS */
+#define QZK_ZS_XST0(t) ((t) == 0 ? 0u : (t) == 1 ? 512u : 768u)
+#define QZK_ZS_MAXLOG(t) ((t) == 1 ? 8u : 9u)
+#define QZK_ZS_NSYM(t) ((t) == 0 ? 36u : (t) == 1 ? 32u : 53u)
+#define QZK_ZS_OF_PREDEF 29u        /* the codes the predefined offset distribution has */
+#define QZK_ZS_DESCB 96u            /* a description: 4 + 53 x 10 bits and at most 86 bits of zero runs are 78 bytes */
+
+/* a chunk's own tables, symbols at SY0(t) as in qzk_zs_tabs, states at XST0(t); what lanes 0-2 leave for the wave */
+typedef struct {
+    uint16_t st[1280];
+    uint32_t dnb[128]; int32_t dfs[128];
+    uint8_t spread[1280];
+    uint16_t cnt[128]; int16_t norm[128];
+    uint32_t hist[128];
+    uint16_t sbits[3][64];
+    uint8_t desc[3][QZK_ZS_DESCB];
+    uint32_t log[3], dsz[3], mode[3], top[3], cost[6];      /* mode: 0 Predefined, 1 RLE, 2 FSE_Compressed; top: the highest code */
+} qzk_zs_xlds;
+#define QZK_ZS_XOFF ((sizeof(qzk_zs_lds) + 15u) & ~(size_t)15u)
+static_assert(QZK_ZS_XOFF + sizeof(qzk_zs_xlds) <= 4 * QZK_L4S_HSIZE, "a chunk's tables lie in what the stage leaves of the parse's table");
+
+/* the offset values of seqs[0..ns) to ofv[i * ofs].  Without `rep` offset + 3.  With it the history of RFC 8878, 3.1.1.5,
+ * which starts at 1, 4, 8: a literal length above 0 has rep1, rep2, rep3 for the values 1, 2, 3; a literal length of 0 has
+ * rep2, rep3 and rep1 - 1 (an offset equal to rep1 has no repeat code then), the lowest value where several fit.  The
+ * recurrence is serial, but it needs no lane: a trip of 64 records sits in the lanes' registers, the wave reads them one by
+ * one (readlane: the record and the history are wave-uniform, the compares scalar) and the record's lane keeps the value.
+ * ofv may be the records' own off fields. */
+QZ_DEV void qzk_zs_offset_values(const qzk_zs_seq *seqs, uint32_t ns, uint32_t *ofv, uint32_t ofs, bool rep, int lane)
+{
+    uint32_t r0 = 1, r1 = 4, r2 = 8;
+    for (uint32_t base = 0; base < ns; base += 64) {
+        const uint32_t i = base + (uint32_t)lane, cnt = qz_uniform(ns - base < 64 ? ns - base : 64);
+        uint32_t key = 0;                                           /* the offset (at most 128 KB), bit 31: literals in front */
+        if (i < ns) key = seqs[i].off | (seqs[i].ll ? 1u << 31 : 0u);
+        uint32_t mine = (key & 0x7fffffffu) + 3;
+        if (rep) {
+            for (uint32_t t = 0; t < cnt; t++) {
+                const uint32_t k = qz_readlane(key, (int)t), o = k & 0x7fffffffu;
+                uint32_t ov;
+                if (k >> 31) {
+                    if (o == r0) ov = 1;
+                    else if (o == r1) { ov = 2; r1 = r0; r0 = o; }
+                    else if (o == r2) { ov = 3; r2 = r1; r1 = r0; r0 = o; }
+                    else { ov = o + 3; r2 = r1; r1 = r0; r0 = o; }
+                } else {
+                    if (o == r1) { ov = 1; r1 = r0; r0 = o; }
+                    else if (o == r2) { ov = 2; r2 = r1; r1 = r0; r0 = o; }
+                    else if (o == r0 - 1) { ov = 3; r2 = r1; r1 = r0; r0 = o; }        /* o >= 1: never a 0 out of rep1 == 1 */
+                    else { ov = o + 3; r2 = r1; r1 = r0; r0 = o; }
+                }
+                if ((uint32_t)lane == t) mine = ov;
+            }
+        }
+        if (i < ns) ofv[(uint64_t)i * ofs] = mine;
+    }
+    qz_wave_sync();                                                 /* the values are other lanes' stores */
+}
+
+/* the table description of norm[0..nsym) (RFC 8878, 4.1.1) into desc; returns its size.  One lane. */
+QZ_DEV uint32_t qzk_zs_ncount(const int16_t *norm, uint32_t nsym, uint32_t log, uint8_t *desc)
+{
+    const uint32_t size = 1u << log;
+    uint32_t dp = 0;
+    uint64_t acc = log - 5; uint32_t nacc = 4;
+    int32_t remaining = (int32_t)size + 1, threshold = (int32_t)size; uint32_t nbits = log + 1;
+    uint32_t s = 0; bool prev0 = false;
+    while (s < nsym && remaining > 1) {
+        if (prev0) {                                                /* how many more zeros follow: 2 bits, 3 says "and then" */
+            uint32_t start = s;
+            while (s < nsym && !norm[s]) s++;
+            while (s >= start + 3) { start += 3; acc |= 3ull << nacc; nacc += 2; }
+            acc |= (uint64_t)(s - start) << nacc; nacc += 2;
+        }
+        int32_t c = norm[s++];
+        const int32_t max = (2 * threshold - 1) - remaining;
+        remaining -= c;
+        c++;
+        if (c >= threshold) c += max;
+        acc |= (uint64_t)c << nacc; nacc += nbits;
+        if (c < max) nacc--;                                        /* the short form below the threshold */
+        prev0 = c == 1;
+        while (remaining < threshold) { nbits--; threshold >>= 1; }
+        while (nacc >= 8) { if (dp < QZK_ZS_DESCB) desc[dp] = (uint8_t)acc; dp++; acc >>= 8; nacc -= 8; }
+    }
+    if (nacc) { if (dp < QZK_ZS_DESCB) desc[dp] = (uint8_t)acc; dp++; }
+    return dp;
+}
+
+/* table t of a chunk of ns sequences from its histogram: the mode so far (RLE, Predefined, or 2 for "FSE_Compressed if the
+ * walk finds it cheaper"), and for 2 the accuracy, the counts, the description and the encoding table.  One lane per table.
+ *   accuracy  log2(ns - 1) - 2 kept in 5 .. 9 (offsets: 5 .. 8), and never below log2 of the codes present, rounded up
+ *   counts    count * 2^accuracy / ns rounded to nearest, at least 1 for a code that occurs; what the sum then misses goes to
+ *             the most frequent code, what it has too much is taken from the then most frequent one, one at a time (the
+ *             lower code among equals).  No "less than one" entries. */
+QZ_DEV void qzk_zs_plan(qzk_zs_xlds *X, uint32_t t, uint32_t ns, bool fse)
+{
+    const uint32_t sy0 = QZK_ZS_SY0(t);
+    const uint32_t *h = X->hist + sy0;
+    uint32_t present = 0, top = 0;
+    for (uint32_t s = 0; s < QZK_ZS_NSYM(t); s++) if (h[s]) { present++; top = s; }
+    X->top[t] = top; X->dsz[t] = 0; X->log[t] = QZK_ZS_LOG(t);
+    if (present == 1) { X->mode[t] = 1; return; }
+    if (!fse) { X->mode[t] = 0; return; }
+    X->mode[t] = 2;
+    uint32_t log = qzk_zs_hb(ns - 1);                               /* two codes: ns >= 2 */
+    log = log > 7 ? log - 2 : 5;
+    if (log > QZK_ZS_MAXLOG(t)) log = QZK_ZS_MAXLOG(t);
+    if (log < qzk_zs_hb(present - 1) + 1) log = qzk_zs_hb(present - 1) + 1;
+    const uint32_t size = 1u << log, nsym = top + 1;
+    int16_t *norm = X->norm + sy0;
+    int32_t sum = 0;
+    for (uint32_t s = 0; s < nsym; s++) {
+        int32_t n = h[s] ? (int32_t)((h[s] * size + ns / 2) / ns) : 0;
+        if (h[s] && n == 0) n = 1;
+        norm[s] = (int16_t)n; sum += n;
+    }
+    while (sum != (int32_t)size) {
+        uint32_t best = 0;
+        for (uint32_t s = 1; s < nsym; s++) if (norm[s] > norm[best]) best = s;
+        if (sum < (int32_t)size) { norm[best] = (int16_t)(norm[best] + ((int32_t)size - sum)); sum = (int32_t)size; }
+        else { norm[best]--; sum--; }                               /* the sum is above 2^accuracy >= present: the largest is above 1 */
+    }
+    X->log[t] = log;
+    X->dsz[t] = qzk_zs_ncount(norm, nsym, log, X->desc[t]);
+    qzk_zs_fse_build(norm, nsym, log, X->st + QZK_ZS_XST0(t), X->dnb + sy0, X->dfs + sy0, X->spread + QZK_ZS_XST0(t), X->cnt + sy0);
+}
+
+/* qzk_zs_sequences with `flags` (not 0): the offset values go to ofv[i * ofs] first, and each table is RLE when all codes
+ * are one, else the cheaper of Predefined and FSE_Compressed by an exact count: lanes 0-2 walk the chains of the chunk's own
+ * tables, lanes 3-5 those of the predefined ones, each adds up the state bits, the final state and the description; the
+ * extra bits are the same either way.  On equal cost Predefined.  A code the predefined distribution does not have leaves
+ * FSE_Compressed.  A trip's bits: the state bits are at most 26 a sequence where they were 17, and the extra bits of
+ * lengths that add up to 128 KB at most stay under 1280 a trip, so the packer's staging area holds them. */
+QZ_DEV uint32_t qzk_zs_sequences_x(qzk_zs_lds *S, qzk_zs_xlds *X, const qzk_zs_tabs *T, const qzk_zs_seq *seqs, uint32_t ns,
+                                   uint32_t *ofv, uint32_t ofs, uint32_t flags, uint8_t *out, uint32_t cap, int lane)
+{
+    if (cap < 8) return QZK_ZS_OVER;
+    if (ns == 0) { if (lane == 0) out[0] = 0; return 1; }
+    uint32_t op;
+    if (ns < 128) { if (lane == 0) out[0] = (uint8_t)ns; op = 1; }
+    else if (ns < 0x7f00) { if (lane == 0) { out[0] = (uint8_t)((ns >> 8) + 128); out[1] = (uint8_t)ns; } op = 2; }
+    else { if (lane == 0) { out[0] = 255; out[1] = (uint8_t)(ns - 0x7f00); out[2] = (uint8_t)((ns - 0x7f00) >> 8); } op = 3; }
+    qzk_zs_offset_values(seqs, ns, ofv, ofs, (flags & QZK_ZS_SEQ_REP) != 0, lane);
+    for (uint32_t i = (uint32_t)lane; i < 128; i += 64) X->hist[i] = 0;
+    qz_lds_sync();
+    for (uint32_t i = (uint32_t)lane; i < ns; i += 64) {
+        const qzk_zs_codes c = qzk_zs_code_v(seqs[i].ll, seqs[i].ml, ofv[(uint64_t)i * ofs]);
+        atomicAdd(&X->hist[QZK_ZS_SY0(0) + c.llc], 1u); atomicAdd(&X->hist[QZK_ZS_SY0(1) + c.ofc], 1u); atomicAdd(&X->hist[QZK_ZS_SY0(2) + c.mlc], 1u);
+    }
+    qz_lds_sync();
+    if (lane < 3) qzk_zs_plan(X, (uint32_t)lane, ns, (flags & QZK_ZS_SEQ_FSE) != 0);
+    qz_lds_sync();
+    const int tl = lane < 6 ? lane % 3 : 0;
+    if (X->mode[0] == 2 || X->mode[1] == 2 || X->mode[2] == 2) {    /* the walk that counts */
+        const bool own = lane < 3;
+        const bool walks = lane < 6 && X->mode[tl] == 2 && (own || tl != QZK_ZS_OF || X->top[QZK_ZS_OF] < QZK_ZS_OF_PREDEF);
+        const uint16_t *st = own ? X->st + QZK_ZS_XST0(tl) : T->st + QZK_ZS_ST0(tl);
+        const uint32_t *dnb = (own ? X->dnb : T->dnb) + QZK_ZS_SY0(tl);
+        const int32_t *dfs = (own ? X->dfs : T->dfs) + QZK_ZS_SY0(tl);
+        uint32_t x = 0, bits = own ? X->log[tl] + 8 * X->dsz[tl] : QZK_ZS_LOG(tl);
+        for (uint32_t base = 0; base < ns; base += 64) {
+            const uint32_t j = base + (uint32_t)lane, cnt = ns - base < 64 ? ns - base : 64;
+            qzk_zs_codes c = { 0, 0, 0, 0, 0, 0 };
+            if (j < ns) c = qzk_zs_code_v(seqs[ns - 1 - j].ll, seqs[ns - 1 - j].ml, ofv[(uint64_t)(ns - 1 - j) * ofs]);
+            S->code[QZK_ZS_LL][lane] = (uint8_t)c.llc; S->code[QZK_ZS_OF][lane] = (uint8_t)c.ofc; S->code[QZK_ZS_ML][lane] = (uint8_t)c.mlc;
+            qz_lds_sync();
+            if (walks) {
+                for (uint32_t t = 0; t < cnt; t++) {
+                    const uint32_t s = S->code[tl][t];
+                    if (base + t == 0) x = qzk_zs_fse_init(st, dnb, dfs, s);
+                    else {
+                        const uint32_t nb = (x + dnb[s]) >> 16;
+                        bits += nb;
+                        x = st[(int32_t)(x >> nb) + dfs[s]];
+                    }
+                }
+            }
+            qz_lds_sync();
+        }
+        if (lane < 6) X->cost[lane] = walks ? bits : 0xffffffffu;
+        qz_lds_sync();
+        if (lane < 3 && X->mode[lane] == 2 && !(X->cost[lane] < X->cost[lane + 3])) X->mode[lane] = 0;
+        qz_lds_sync();
+    }
+    const uint32_t mll = X->mode[QZK_ZS_LL], mof = X->mode[QZK_ZS_OF], mml = X->mode[QZK_ZS_ML];
+    /* the modes byte, then per table nothing, its one code, or its description: all of it or none */
+    uint32_t hdr = 1;
+    for (uint32_t t = 0; t < 3; t++) hdr += X->mode[t] == 1 ? 1u : X->mode[t] == 2 ? X->dsz[t] : 0u;
+    if (op + hdr + 1 > cap) return QZK_ZS_OVER;
+    if (lane == 0) out[op] = (uint8_t)(mll << 6 | mof << 4 | mml << 2);
+    op++;
+    for (uint32_t t = 0; t < 3; t++) {
+        if (X->mode[t] == 1) { if (lane == 0) out[op] = (uint8_t)X->top[t]; op++; }
+        else if (X->mode[t] == 2) {
+            for (uint32_t i = (uint32_t)lane; i < X->dsz[t]; i += 64) out[op + i] = X->desc[t][i];
+            op += X->dsz[t];
+        }
+    }
+    /* lanes 0, 1, 2 own the LL, OF, ML chain, each in the table chosen */
+    const int cl = lane < 3 ? lane : 0;
+    const bool myrle = X->mode[cl] == 1, mine = X->mode[cl] == 2;
+    const uint16_t *st = mine ? X->st + QZK_ZS_XST0(cl) : T->st + QZK_ZS_ST0(cl);
+    const uint32_t *dnb = (mine ? X->dnb : T->dnb) + QZK_ZS_SY0(cl);
+    const int32_t *dfs = (mine ? X->dfs : T->dfs) + QZK_ZS_SY0(cl);
+    uint32_t x = 0;
+    qzk_zs_bw w = { out + op, 0, cap - op, 0, 0, 0 };
+    for (uint32_t base = 0; base < ns; base += 64) {                /* trip by trip from the last sequence back */
+        const uint32_t j = base + (uint32_t)lane, cnt = ns - base < 64 ? ns - base : 64;
+        qzk_zs_codes c = { 0, 0, 0, 0, 0, 0 };
+        if (j < ns) c = qzk_zs_code_v(seqs[ns - 1 - j].ll, seqs[ns - 1 - j].ml, ofv[(uint64_t)(ns - 1 - j) * ofs]);
+        S->code[QZK_ZS_LL][lane] = (uint8_t)c.llc; S->code[QZK_ZS_OF][lane] = (uint8_t)c.ofc; S->code[QZK_ZS_ML][lane] = (uint8_t)c.mlc;
+        qz_lds_sync();
+        if (lane < 3) {
+            for (uint32_t t = 0; t < cnt; t++) {
+                uint32_t v = 0, nb = 0;
+                if (!myrle) {
+                    const uint32_t s = S->code[lane][t];
+                    if (base + t == 0) x = qzk_zs_fse_init(st, dnb, dfs, s);
+                    else {
+                        nb = (x + dnb[s]) >> 16;
+                        v = x & ((1u << nb) - 1);
+                        x = st[(int32_t)(x >> nb) + dfs[s]];
+                    }
+                }
+                X->sbits[lane][t] = (uint16_t)v; S->snb[lane][t] = (uint8_t)nb;
+            }
+        }
+        qz_lds_sync();
+        uint64_t a = 0, b = 0; uint32_t na = 0, nb = 0;
+        if (j < ns) {
+            a = X->sbits[QZK_ZS_OF][lane]; na = S->snb[QZK_ZS_OF][lane];
+            a |= (uint64_t)X->sbits[QZK_ZS_ML][lane] << na; na += S->snb[QZK_ZS_ML][lane];
+            a |= (uint64_t)X->sbits[QZK_ZS_LL][lane] << na; na += S->snb[QZK_ZS_LL][lane];
+            a |= (uint64_t)c.llx << na; na += QZK_ZS_LL_BITS[c.llc];
+            b = c.mlx; nb = QZK_ZS_ML_BITS[c.mlc];
+            b |= (uint64_t)c.ofx << nb; nb += c.ofc;
+        }
+        qzk_zs_pack(S, &w, a, na, b, nb, lane);
+    }
+    /* the final states: ML, OF, LL, each as wide as its table's accuracy, then the closing bit */
+    const uint32_t xl = qz_readlane(x, 0), xo = qz_readlane(x, 1), xm = qz_readlane(x, 2);
+    uint64_t a = 0; uint32_t na = 0;
+    if (lane == 0) {
+        const uint32_t gl = mll == 2 ? X->log[QZK_ZS_LL] : QZK_ZS_LOG(QZK_ZS_LL), go = mof == 2 ? X->log[QZK_ZS_OF] : QZK_ZS_LOG(QZK_ZS_OF),
+                       gm = mml == 2 ? X->log[QZK_ZS_ML] : QZK_ZS_LOG(QZK_ZS_ML);
+        if (mml != 1) { a |= (uint64_t)(xm & ((1u << gm) - 1)) << na; na += gm; }
+        if (mof != 1) { a |= (uint64_t)(xo & ((1u << go) - 1)) << na; na += go; }
+        if (mll != 1) { a |= (uint64_t)(xl & ((1u << gl) - 1)) << na; na += gl; }
+        a |= 1ull << na; na++;
+    }
+    qzk_zs_pack(S, &w, a, na, 0, 0, lane);
+    qzk_zs_close(&w, lane);
+    return w.over ? QZK_ZS_OVER : op + w.op;
+}
+
 /* ------------------------------------------------------------------ frames */
 /* records someone else made: true when every match is 3 .. 128 KB long and starts 1 .. (bytes before it) back, the literal
  * lengths stay inside the nl literals, and lengths and trailing literals add up to n */
@@ -596,8 +871,10 @@ QZ_DEV void qzk_zs_rebuild(uint8_t *dst, const qzk_zs_seq *seqs, uint32_t ns, co
 
 /* one frame of n >= 1 bytes at out (QZK_ZS_BOUND(n) + QZK_ZS_SLACK bytes are there); src: the content, NULL when the records
  * are all there is.  Returns the frame's size, at most QZK_ZS_BOUND(n). */
-QZ_DEV uint32_t qzk_zs_frame(qzk_zs_lds *S, const qzk_zs_tabs *T, const uint8_t *src, uint32_t n, const qzk_zs_seq *seqs, uint32_t ns,
-                             const uint8_t *lits, uint32_t nl, uint8_t *out, int lane)
+/* SEQ: the sequences section is qzk_zs_sequences_x's under `flags` (X, ofv and ofs are its arguments), else qzk_zs_sequences' */
+template <bool SEQ>
+QZ_DEV uint32_t qzk_zs_frame(qzk_zs_lds *S, qzk_zs_xlds *X, const qzk_zs_tabs *T, const uint8_t *src, uint32_t n, const qzk_zs_seq *seqs,
+                             uint32_t ns, uint32_t *ofv, uint32_t ofs, uint32_t flags, const uint8_t *lits, uint32_t nl, uint8_t *out, int lane)
 {
     const uint32_t fb = n < 256 ? 1u : n < 65792 ? 2u : 4u;
     if (lane == 0) {
@@ -611,7 +888,8 @@ QZ_DEV uint32_t qzk_zs_frame(qzk_zs_lds *S, const qzk_zs_tabs *T, const uint8_t 
     uint32_t bsz = QZK_ZS_OVER;
     const uint32_t lsz = qzk_zs_literals(S, lits, nl, body, lane);
     if (lsz < n) {
-        const uint32_t ssz = qzk_zs_sequences(S, T, seqs, ns, body + lsz, n - lsz, lane);
+        const uint32_t ssz = SEQ ? qzk_zs_sequences_x(S, X, T, seqs, ns, ofv, ofs, flags, body + lsz, n - lsz, lane)
+                                 : qzk_zs_sequences(S, T, seqs, ns, body + lsz, n - lsz, lane);
         if (ssz != QZK_ZS_OVER && lsz + ssz < n) bsz = lsz + ssz;
     }
     uint32_t bh;
@@ -632,14 +910,13 @@ QZ_DEV uint32_t qzk_zs_frame(qzk_zs_lds *S, const qzk_zs_tabs *T, const uint8_t 
 #define QZK_ZS_WAVEB(block_sz) (QZK_ZS_LITB(block_sz) + ((((block_sz) / 3u + 1u) * 12u + 15u) & ~15u))
 
 /* Kz: persistent single-wave workgroups pull chunk numbers (as qzk_lz4s_pull_kernel); chunk b of the launch goes to slot b as
- * one frame, out_len[b] = its size.  scratch: QZK_ZS_WAVEB(block_sz) bytes per workgroup of the launch. */
-QZ_KERNEL_MAX(64) qzk_zstd_pull_kernel(const uint8_t *src, uint64_t src_len, uint32_t block_sz, uint32_t nblocks, uint8_t *slots,
-                                       uint32_t stride, uint32_t *out_len, uint32_t mm, uint32_t *counter, uint8_t *scratch)
+ * one frame, out_len[b] = its size.  scratch: QZK_ZS_WAVEB(block_sz) bytes per workgroup of the launch.  With SEQ the
+ * offset values overwrite the records' offsets in the wave's scratch, and the chunk's tables lie behind the stage's LDS. */
+template <bool SEQ>
+QZ_DEV void qzk_zstd_pull(uint32_t *table, const qzk_zs_tabs *T, const uint8_t *src, uint64_t src_len, uint32_t block_sz, uint32_t nblocks,
+                          uint8_t *slots, uint32_t stride, uint32_t *out_len, uint32_t mm, uint32_t *counter, uint8_t *scratch, uint32_t flags)
 {
-    QZ_LDS uint32_t table[QZK_L4S_HSIZE];
-    QZ_LDS qzk_zs_tabs T;
     const int lane = qz_lane();
-    qzk_zs_tabs_init(&T, lane);
     uint8_t *lits = scratch + (uint64_t)blockIdx.x * QZK_ZS_WAVEB(block_sz);
     qzk_zs_seq *seqs = (qzk_zs_seq *)(lits + QZK_ZS_LITB(block_sz));
     for (;;) {
@@ -651,33 +928,72 @@ QZ_KERNEL_MAX(64) qzk_zstd_pull_kernel(const uint8_t *src, uint64_t src_len, uin
         qzk_zs_rec e = { seqs, lits, 0, 0 };
         qzk_l4s_parse(src + off, n, e, mm, table, lane);
         qz_wave_sync();                                             /* the records and literals are other lanes' stores */
-        const uint32_t c = qzk_zs_frame((qzk_zs_lds *)table, &T, src + off, n, seqs, e.ns, lits, e.nl, slots + (uint64_t)b * stride, lane);
+        const uint32_t c = qzk_zs_frame<SEQ>((qzk_zs_lds *)table, (qzk_zs_xlds *)((uint8_t *)table + QZK_ZS_XOFF), T, src + off, n, seqs, e.ns,
+                                             &seqs[0].off, 3, flags, lits, e.nl, slots + (uint64_t)b * stride, lane);
         out_len[b] = c;                 /* wave-uniform: every lane stores the same word */
         qz_wave_sync();
     }
 }
+QZ_KERNEL_MAX(64) qzk_zstd_pull_kernel(const uint8_t *src, uint64_t src_len, uint32_t block_sz, uint32_t nblocks, uint8_t *slots,
+                                       uint32_t stride, uint32_t *out_len, uint32_t mm, uint32_t *counter, uint8_t *scratch)
+{
+    QZ_LDS uint32_t table[QZK_L4S_HSIZE];
+    QZ_LDS qzk_zs_tabs T;
+    qzk_zs_tabs_init(&T, qz_lane());
+    qzk_zstd_pull<false>(table, &T, src, src_len, block_sz, nblocks, slots, stride, out_len, mm, counter, scratch, 0);
+}
+/* ... with seq_flags (not 0): a kernel of its own, so that the one above stays what it was */
+QZ_KERNEL_MAX(64) qzk_zstd_pull_seq_kernel(const uint8_t *src, uint64_t src_len, uint32_t block_sz, uint32_t nblocks, uint8_t *slots,
+                                           uint32_t stride, uint32_t *out_len, uint32_t mm, uint32_t *counter, uint8_t *scratch,
+                                           uint32_t seq_flags)
+{
+    QZ_LDS uint32_t table[QZK_L4S_HSIZE];
+    QZ_LDS qzk_zs_tabs T;
+    qzk_zs_tabs_init(&T, qz_lane());
+    qzk_zstd_pull<true>(table, &T, src, src_len, block_sz, nblocks, slots, stride, out_len, mm, counter, scratch, seq_flags);
+}
 
 /* the entropy stage alone, a wave per frame of the caller's records: out_len[b] = the frame's size, or 0 and *bad set when
- * the records are not a frame's (qzk_zs_check) */
-QZ_KERNEL_MAX(64) qzk_zstd_encode_kernel(const uint8_t *lits, const qzk_zs_seq *seqs, const qzk_zs_fdesc *desc, uint32_t nframes,
-                                         uint8_t *slots, uint32_t stride, uint32_t *out_len, uint32_t *bad, uint32_t *counter)
+ * the records are not a frame's (qzk_zs_check).  With SEQ the offset values go to ofv + workgroup * ofv_words: the caller's
+ * records are not written. */
+template <bool SEQ>
+QZ_DEV void qzk_zstd_encode(qzk_zs_lds *S, qzk_zs_xlds *X, const qzk_zs_tabs *T, const uint8_t *lits, const qzk_zs_seq *seqs,
+                            const qzk_zs_fdesc *desc, uint32_t nframes, uint8_t *slots, uint32_t stride, uint32_t *out_len, uint32_t *bad,
+                            uint32_t *counter, uint32_t *ofv, uint32_t ofv_words, uint32_t flags)
 {
-    QZ_LDS qzk_zs_lds S;
-    QZ_LDS qzk_zs_tabs T;
     const int lane = qz_lane();
-    qzk_zs_tabs_init(&T, lane);
+    uint32_t *myofv = SEQ ? ofv + (uint64_t)blockIdx.x * ofv_words : NULL;
     for (;;) {
         uint32_t b = atomicAdd(counter, lane == 0 ? 1u : 0u);
         b = qz_readfirstlane(b);
         if (b >= nframes) break;
         const qzk_zs_fdesc d = desc[b];
         uint32_t c = 0;
-        if (qzk_zs_check(seqs + d.seq0, d.nseq, d.nlit, d.content, lane))
-            c = qzk_zs_frame(&S, &T, NULL, d.content, seqs + d.seq0, d.nseq, lits + d.lit0, d.nlit, slots + (uint64_t)b * stride, lane);
+        if (qzk_zs_check(seqs + d.seq0, d.nseq, d.nlit, d.content, lane) && (!SEQ || d.nseq <= ofv_words))
+            c = qzk_zs_frame<SEQ>(S, X, T, NULL, d.content, seqs + d.seq0, d.nseq, myofv, 1, flags, lits + d.lit0, d.nlit,
+                                  slots + (uint64_t)b * stride, lane);
         else if (lane == 0) atomicOr(bad, 1u);
         out_len[b] = c;
         qz_wave_sync();
     }
+}
+QZ_KERNEL_MAX(64) qzk_zstd_encode_kernel(const uint8_t *lits, const qzk_zs_seq *seqs, const qzk_zs_fdesc *desc, uint32_t nframes,
+                                         uint8_t *slots, uint32_t stride, uint32_t *out_len, uint32_t *bad, uint32_t *counter)
+{
+    QZ_LDS qzk_zs_lds S;
+    QZ_LDS qzk_zs_tabs T;
+    qzk_zs_tabs_init(&T, qz_lane());
+    qzk_zstd_encode<false>(&S, NULL, &T, lits, seqs, desc, nframes, slots, stride, out_len, bad, counter, NULL, 0, 0);
+}
+QZ_KERNEL_MAX(64) qzk_zstd_encode_seq_kernel(const uint8_t *lits, const qzk_zs_seq *seqs, const qzk_zs_fdesc *desc, uint32_t nframes,
+                                             uint8_t *slots, uint32_t stride, uint32_t *out_len, uint32_t *bad, uint32_t *counter,
+                                             uint32_t *ofv, uint32_t ofv_words, uint32_t seq_flags)
+{
+    QZ_LDS qzk_zs_lds S;
+    QZ_LDS qzk_zs_xlds X;
+    QZ_LDS qzk_zs_tabs T;
+    qzk_zs_tabs_init(&T, qz_lane());
+    qzk_zstd_encode<true>(&S, &X, &T, lits, seqs, desc, nframes, slots, stride, out_len, bad, counter, ofv, ofv_words, seq_flags);
 }
 
 #endif
