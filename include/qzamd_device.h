@@ -295,6 +295,14 @@ int qzd_zstd_compress_frames_ex(qzd_ctx *ctx, const uint8_t *d_src, uint64_t n, 
 int qzd_zstd_encode_frames_ex(qzd_ctx *ctx, const uint8_t *d_literals, const uint32_t *d_seqs, const uint32_t *h_desc,
                               uint32_t nframes, uint8_t *d_dst, uint64_t dst_cap, uint64_t *h_out_len, uint32_t *h_frame_len,
                               uint32_t seq_flags);
+/* qzd_zstd_compress_frames_ex with parse_depth, the depth of include/qzamd_zstd_parse.h: 0 is the call above, byte for
+ * byte; 1 .. 256 - the sequences come from the hash-chain lazy parse with that many search attempts per position (offsets
+ * back to the chunk's start, repeat offsets weighed in), coded under seq_flags as above.  QZD_ERR_PARAM for a depth above
+ * 256; everything else, the bound and the frame layout as above.  The context keeps about 19 bytes of scratch per input
+ * byte of a round ("Parse depth"). */
+int qzd_zstd_compress_frames_parse(qzd_ctx *ctx, const uint8_t *d_src, uint64_t n, uint32_t block_sz, uint32_t mini_match,
+                                   int level, uint8_t *d_dst, uint64_t dst_cap, uint64_t *h_out_len, uint32_t *h_frame_len,
+                                   uint32_t seq_flags, uint32_t parse_depth);
 /* decode nsegs frames (any block mode; block checksums and the content checksum verified on the GPU); replaces
  * LZ4F_decompress, src/qatzip_sw.c:496, and answers as it does: a wrong block checksum is a data error whether or not the
  * frame has a content checksum, and in a frame of independent blocks (FLG bit 5) a match that reaches in front of its own

@@ -78,6 +78,7 @@ def load(build_if_missing=True):
     L.qzd_zstd_encode_frames.argtypes = [vp, u8p, vp, vp, C.c_uint32, u8p, C.c_uint64, C.POINTER(C.c_uint64), vp]
     L.qzd_zstd_compress_frames_ex.argtypes = L.qzd_zstd_compress_frames.argtypes + [C.c_uint32]
     L.qzd_zstd_encode_frames_ex.argtypes = L.qzd_zstd_encode_frames.argtypes + [C.c_uint32]
+    L.qzd_zstd_compress_frames_parse.argtypes = L.qzd_zstd_compress_frames.argtypes + [C.c_uint32, C.c_uint32]
     L.qzd_zstd_decompress_frames.argtypes = [vp, u8p, u8p, vp, C.c_uint32, vp]
     L.qzd_chunk_lens.argtypes = [vp, vp, C.c_uint32]
     L.qzd_shard_root_create.argtypes = [vp, C.c_uint32, C.c_uint64, C.c_char_p, C.POINTER(vp)]
@@ -129,7 +130,7 @@ def exported_symbols():
             "qzd_lz4hc_compress_frames", "qzd_lz4hc_compress_frames_hw", "qzd_lz4hc_compress_linked",
             "qzd_lz4s_bound", "qzd_lz4s_compress_blocks",
             "qzd_zstd_bound", "qzd_zstd_compress_frames", "qzd_zstd_encode_frames", "qzd_zstd_decompress_frames",
-            "qzd_zstd_compress_frames_ex", "qzd_zstd_encode_frames_ex",
+            "qzd_zstd_compress_frames_ex", "qzd_zstd_encode_frames_ex", "qzd_zstd_compress_frames_parse",
             "qzd_crcn_ranges", "qzd_xxh32_ranges", "qzd_blocks_compress", "qzd_blocks_decompress",
             "qzd_crc32_fold", "qzd_pcie_peak", "qzd_rccl_unique_id", "qzd_rccl_create", "qzd_rccl_gather", "qzd_rccl_close"]
 
@@ -334,15 +335,20 @@ class Context:
                                                   d_dst.nbytes if dst_cap is None else dst_cap, C.byref(ol), lens.ctypes.data))
         return ol.value, lens[:nb]
 
-    def zstd_compress_frames(self, d_src, n, d_dst, block_sz=65536, mini_match=3, level=1, dst_cap=None, seq_flags=None):
+    def zstd_compress_frames(self, d_src, n, d_dst, block_sz=65536, mini_match=3, level=1, dst_cap=None, seq_flags=None,
+                             parse_depth=None):
         """every block_sz bytes one zstd frame (the LZ4s parse, entropy-coded on the device) -> (out_len, per-frame lengths).
-        seq_flags (the bits of include/qzamd_zstd_seq.h): through qzd_zstd_compress_frames_ex"""
+        seq_flags (the bits of include/qzamd_zstd_seq.h): through qzd_zstd_compress_frames_ex; parse_depth (the depth of
+        include/qzamd_zstd_parse.h): through qzd_zstd_compress_frames_parse, with seq_flags or 0"""
         nb = (n + block_sz - 1) // block_sz
         ol = C.c_uint64(0)
         lens = np.zeros(max(nb, 1), np.uint32)
         args = (self.h, d_src.ptr, n, block_sz, mini_match, level, d_dst.ptr, d_dst.nbytes if dst_cap is None else dst_cap,
                 C.byref(ol), lens.ctypes.data)
-        self._chk(self.L.qzd_zstd_compress_frames(*args) if seq_flags is None else self.L.qzd_zstd_compress_frames_ex(*args, seq_flags))
+        if parse_depth is not None:
+            self._chk(self.L.qzd_zstd_compress_frames_parse(*args, seq_flags or 0, parse_depth))
+        else:
+            self._chk(self.L.qzd_zstd_compress_frames(*args) if seq_flags is None else self.L.qzd_zstd_compress_frames_ex(*args, seq_flags))
         return ol.value, lens[:nb]
 
     def zstd_encode_frames(self, d_literals, d_seqs, desc, d_dst, dst_cap=None, seq_flags=None):

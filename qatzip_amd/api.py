@@ -142,6 +142,7 @@ def lib():
         L.qzGetSessionCrc32Config.argtypes = [P(QzSession), P(QzCrc32Config)]
         L.qzSetSessionCrc32Config.argtypes = [P(QzSession), P(QzCrc32Config)]
         L.qzSetSessionZstdSeqAMD.argtypes = [P(QzSession), C.c_uint]
+        L.qzSetSessionZstdParseAMD.argtypes = [P(QzSession), C.c_uint]
         _bound = True
     return L
 
@@ -292,6 +293,11 @@ class Session:
     def set_zstd_seq(self, flags):
         """qzSetSessionZstdSeqAMD (include/qzamd_zstd_seq.h): QZ_ZSTD_SEQ_FSE_TABLES | QZ_ZSTD_SEQ_REPEAT_OFFSETS, 0 for neither"""
         return self.L.qzSetSessionZstdSeqAMD(C.byref(self.s), flags)
+
+    def set_zstd_parse(self, depth):
+        """qzSetSessionZstdParseAMD (include/qzamd_zstd_parse.h): 0 the default parse, 1 .. 256 the search attempts per position
+        of the hash-chain lazy parse"""
+        return self.L.qzSetSessionZstdParseAMD(C.byref(self.s), depth)
 
     def set_crc32(self, polynomial, initial_value, reflect_in, reflect_out, xor_out):
         g = QzCrc32Config(polynomial, initial_value, reflect_in, reflect_out, xor_out)

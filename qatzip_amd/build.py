@@ -19,6 +19,7 @@ def _sources():
     out.append(os.path.join(os.path.dirname(HERE), "include", "qzamd_zstd.h"))
     out.append(os.path.join(os.path.dirname(HERE), "include", "qzamd_zstd_dec.h"))
     out.append(os.path.join(os.path.dirname(HERE), "include", "qzamd_zstd_seq.h"))
+    out.append(os.path.join(os.path.dirname(HERE), "include", "qzamd_zstd_parse.h"))
     q = os.path.join(os.path.dirname(HERE), "include", "qatzip.h")
     if os.path.exists(q):
         out.append(q)

@@ -18,6 +18,7 @@
 #include "qzamd_zstd.h"
 #include "qzamd_zstd_dec.h"
 #include "qzamd_zstd_seq.h"
+#include "qzamd_zstd_parse.h"
 #include "../csrc/qzd_zstdd_host.h"
 
 #define PIECE_BYTES (64u * 1024 * 1024)
@@ -35,6 +36,9 @@ static void usage(FILE *f)
                "  --seq-tables the sequence tables of a frame Predefined, RLE or FSE_Compressed, whichever is smallest\n"
                "  --repeat-offsets\n"
                "               offsets coded against the repeat-offset history\n"
+               "  --parse-depth <N>\n"
+               "               0 (default) the parse of LZ4s sessions; 1 .. 256 a hash-chain lazy parse with N search attempts\n"
+               "               per position, offsets back to the chunk's start and repeat offsets weighed in\n"
                "  -d           not offered under this spelling (exit 2): use --decompress, or zstd -d\n"
                "  --decompress <file.zst>\n"
                "               decode <file.zst> (zstd and skippable frames of any writer, no dictionaries) to <file>,\n"
@@ -118,14 +122,22 @@ int main(int argc, char **argv)
     unsigned hw = 65536, level = 1, mm = 3;
     const char *oname = NULL;
     int keep = 0, c, decompress = 0;
-    unsigned seq_flags = 0;
+    unsigned seq_flags = 0, parse_depth = 0;
     static const struct option longopts[] = { { "decompress", no_argument, NULL, 'D' }, { "seq-tables", no_argument, NULL, 'T' },
-                                              { "repeat-offsets", no_argument, NULL, 'R' }, { NULL, 0, NULL, 0 } };
+                                              { "repeat-offsets", no_argument, NULL, 'R' }, { "parse-depth", required_argument, NULL, 'P' },
+                                              { NULL, 0, NULL, 0 } };
     while ((c = getopt_long(argc, argv, "C:L:m:o:kdh", longopts, NULL)) != -1) {
         switch (c) {
         case 'D': decompress = 1; break;
         case 'T': seq_flags |= QZ_ZSTD_SEQ_FSE_TABLES; break;
         case 'R': seq_flags |= QZ_ZSTD_SEQ_REPEAT_OFFSETS; break;
+        case 'P': {
+            char *end = NULL;
+            const unsigned long v = strtoul(optarg, &end, 0);
+            if (!*optarg || *end || v > QZ_ZSTD_PARSE_DEPTH_MAX) { fprintf(stderr, "qzstd-amd: --parse-depth takes 0 .. %u\n", QZ_ZSTD_PARSE_DEPTH_MAX); return 2; }
+            parse_depth = (unsigned)v;
+            break;
+        }
         case 'C': hw = (unsigned)strtoul(optarg, NULL, 0); break;
         case 'L': level = (unsigned)strtoul(optarg, NULL, 0); break;
         case 'm': mm = (unsigned)strtoul(optarg, NULL, 0); break;
@@ -189,6 +201,7 @@ int main(int argc, char **argv)
     rc = qzSetupSessionZstdAMD(&sess, &p);
     if (rc != QZ_OK) { fprintf(stderr, "qzstd-amd: these parameters are refused (%d): -C a power of two in 1024 .. 131072, -L 1-12, -m 3 or 4\n", rc); return 2; }
     if (seq_flags && qzSetSessionZstdSeqAMD(&sess, seq_flags) != QZ_OK) { fprintf(stderr, "qzstd-amd: the sequence options are refused\n"); qzTeardownSession(&sess); return 2; }
+    if (parse_depth && qzSetSessionZstdParseAMD(&sess, parse_depth) != QZ_OK) { fprintf(stderr, "qzstd-amd: the parse depth is refused\n"); qzTeardownSession(&sess); return 2; }
 
     int status = 1, created = 0;
     FILE *in = fopen(iname, "rb"), *out = NULL;

@@ -35,6 +35,7 @@
 #include "../../include/qzamd_zstd.h"
 #include "../../include/qzamd_zstd_dec.h"
 #include "../../include/qzamd_zstd_seq.h"
+#include "../../include/qzamd_zstd_parse.h"
 #include "qzd_zstdd_host.h"             /* a zstd frame's extent */
 #include "qz_frame.h"                   /* the F_* formats, bounds, the delivery rule, member framing, the crc folds */
 #include "qz_unframe.h"                 /* ... and of the decompress calls: member headers, sized members, frame plans, the crc folds */
@@ -47,6 +48,7 @@ struct Params {
     bool zstd;                      /* an F_LZ4S session made by qzSetupSessionZstdAMD: the same parse, written as zstd frames */
     bool zstd_dec;                  /* ... made by qzSetupSessionZstdDecAMD: qzDecompress reads zstd frames */
     unsigned zstd_seq;              /* ... how its frames' sequences are coded: the flags of qzSetSessionZstdSeqAMD, 0 at setup */
+    unsigned zstd_parse;            /* ... and how they are found: the depth of qzSetSessionZstdParseAMD, 0 at setup */
 };
 
 struct Sess {
@@ -161,7 +163,7 @@ static int lz4s_to(Params &p, const QzSessionParamsLZ4S_T *s)
     if (s->lz4s_mini_match < 3 || s->lz4s_mini_match > 4) return QZ_PARAMS;
     p = g_def;
     from_common(p, s->common_params);
-    p.fmt = F_LZ4S; p.zstd = false; p.zstd_dec = false; p.zstd_seq = 0;
+    p.fmt = F_LZ4S; p.zstd = false; p.zstd_dec = false; p.zstd_seq = 0; p.zstd_parse = 0;
     p.cb = s->qzCallback; p.cb_ext = s->qzCallback_external; p.lz4s_mini_match = s->lz4s_mini_match;
     return check_common(p, true);
 }
@@ -369,6 +371,16 @@ extern "C" int qzSetSessionZstdSeqAMD(QzSession_T *sess, unsigned int flags)
     if (!s || s->p.fmt != F_LZ4S || !s->p.zstd || (s->p.zstd_dec && s->p.direction != QZ_DIR_BOTH)) return QZ_PARAMS;
     if (flags & ~(QZ_ZSTD_SEQ_FSE_TABLES | QZ_ZSTD_SEQ_REPEAT_OFFSETS)) return QZ_PARAMS;
     s->p.zstd_seq = flags;
+    return QZ_OK;
+}
+
+/* how a zstd session that compresses finds its sequences (include/qzamd_zstd_parse.h); the next qzCompress* call sees it */
+extern "C" int qzSetSessionZstdParseAMD(QzSession_T *sess, unsigned int depth)
+{
+    Sess *s = sess ? (Sess *)sess->internal : NULL;
+    if (!s || s->p.fmt != F_LZ4S || !s->p.zstd || (s->p.zstd_dec && s->p.direction != QZ_DIR_BOTH)) return QZ_PARAMS;
+    if (depth > QZ_ZSTD_PARSE_DEPTH_MAX) return QZ_PARAMS;
+    s->p.zstd_parse = depth;
     return QZ_OK;
 }
 
@@ -634,8 +646,8 @@ static int compress_lz4s(QzSession_T *sess, Sess *s, const unsigned char *src, u
     std::vector<uint32_t> lens(nchunks);
     uint64_t produced = 0;
     /* a zstd session: the same chunks, the same parse, a frame each instead of a block */
-    if ((s->p.zstd ? qzd_zstd_compress_frames_ex(s->ctx, s->d_in, n, hw, s->p.lz4s_mini_match, (int)s->p.comp_lvl, s->d_out, s->out_cap,
-                                                 &produced, lens.data(), s->p.zstd_seq)
+    if ((s->p.zstd ? qzd_zstd_compress_frames_parse(s->ctx, s->d_in, n, hw, s->p.lz4s_mini_match, (int)s->p.comp_lvl, s->d_out, s->out_cap,
+                                                    &produced, lens.data(), s->p.zstd_seq, s->p.zstd_parse)
                    : qzd_lz4s_compress_blocks(s->ctx, s->d_in, n, hw, s->p.lz4s_mini_match, (int)s->p.comp_lvl, s->d_out, s->out_cap,
                                               &produced, lens.data())) != QZD_OK) {
         logmsg(LOG_ERROR, "GPU %s failed: %s\n", s->p.zstd ? "zstd" : "LZ4s", qzd_last_error(s->ctx));

@@ -1311,9 +1311,9 @@ extern "C" int qzd_lz4s_compress_blocks(qzd_ctx *c, const uint8_t *d_src, uint64
 /* per chunk of c bytes 4 + 1 + 4 + 3 + c: a block that would not be smaller than the chunk is written Raw */
 extern "C" uint64_t qzd_zstd_bound(uint64_t n, uint32_t block_sz) { return qzd_zs_bound(n, block_sz); }
 
-extern "C" int qzd_zstd_compress_frames_ex(qzd_ctx *c, const uint8_t *d_src, uint64_t n, uint32_t block_sz, uint32_t mini_match,
-                                           int level, uint8_t *d_dst, uint64_t dst_cap, uint64_t *h_out_len, uint32_t *h_frame_len,
-                                           uint32_t seq_flags)
+/* what the calls that compress to zstd frames check before they launch anything */
+static int zstd_compress_args(qzd_ctx *c, const uint8_t *d_src, uint64_t n, uint32_t block_sz, uint32_t mini_match, int level,
+                              uint8_t *d_dst, uint64_t dst_cap, uint64_t *h_out_len, uint32_t seq_flags)
 {
     if (!c || !d_dst || (n && !d_src) || !h_out_len) return QZD_ERR_PARAM;
     if (!qzd_zs_params_ok(block_sz, mini_match)) {
@@ -1324,6 +1324,14 @@ extern "C" int qzd_zstd_compress_frames_ex(qzd_ctx *c, const uint8_t *d_src, uin
     if (level < 1 || level > 12) { snprintf(c->err, sizeof(c->err), "zstd: levels 1-12 (level %d asked for)", level); return QZD_ERR_UNSUPPORTED; }
     if ((n + block_sz - 1) / block_sz > 0x7fffffffull) { snprintf(c->err, sizeof(c->err), "zstd: too many frames"); return QZD_ERR_UNSUPPORTED; }
     if (dst_cap < qzd_zs_bound(n, block_sz)) { snprintf(c->err, sizeof(c->err), "destination too small"); return QZD_ERR_DSTCAP; }
+    return QZD_OK;
+}
+
+extern "C" int qzd_zstd_compress_frames_ex(qzd_ctx *c, const uint8_t *d_src, uint64_t n, uint32_t block_sz, uint32_t mini_match,
+                                           int level, uint8_t *d_dst, uint64_t dst_cap, uint64_t *h_out_len, uint32_t *h_frame_len,
+                                           uint32_t seq_flags)
+{
+    QZD_TRY(zstd_compress_args(c, d_src, n, block_sz, mini_match, level, d_dst, dst_cap, h_out_len, seq_flags));
     *h_out_len = 0;
     if (!n) return QZD_OK;
     hipSetDevice(c->device);
@@ -1351,6 +1359,46 @@ extern "C" int qzd_zstd_compress_frames(qzd_ctx *c, const uint8_t *d_src, uint64
                                         int level, uint8_t *d_dst, uint64_t dst_cap, uint64_t *h_out_len, uint32_t *h_frame_len)
 {
     return qzd_zstd_compress_frames_ex(c, d_src, n, block_sz, mini_match, level, d_dst, dst_cap, h_out_len, h_frame_len, 0);
+}
+
+/* the frames of qzd_zstd_compress_frames_ex from the sequences of the hash-chain lazy parse (qzk_zstd_parse.h): per round of
+ * the host plan the head tables zeroed, then P1 .. P4 behind one another on the call's stream, a wave per chunk each.  The
+ * round's scratch is the context's (d_lane: it grows to the largest round seen and stays, as the LZ4-HC path's does). */
+#include "qzk_zstd_parse.h"
+#include "qzd_zstd_parse_host.h"
+extern "C" int qzd_zstd_compress_frames_parse(qzd_ctx *c, const uint8_t *d_src, uint64_t n, uint32_t block_sz, uint32_t mini_match,
+                                              int level, uint8_t *d_dst, uint64_t dst_cap, uint64_t *h_out_len, uint32_t *h_frame_len,
+                                              uint32_t seq_flags, uint32_t parse_depth)
+{
+    if (!c) return QZD_ERR_PARAM;
+    if (!qzd_zp_depth_ok(parse_depth)) { snprintf(c->err, sizeof(c->err), "zstd: parse_depth 0 .. 256"); return QZD_ERR_PARAM; }
+    if (parse_depth == 0)
+        return qzd_zstd_compress_frames_ex(c, d_src, n, block_sz, mini_match, level, d_dst, dst_cap, h_out_len, h_frame_len, seq_flags);
+    QZD_TRY(zstd_compress_args(c, d_src, n, block_sz, mini_match, level, d_dst, dst_cap, h_out_len, seq_flags));
+    *h_out_len = 0;
+    if (!n) return QZD_OK;
+    hipSetDevice(c->device);
+    const uint32_t nb = (uint32_t)((n + block_sz - 1) / block_sz);
+    const qzd_zp_plan P = qzd_zp_plan_for(block_sz, nb);
+    const uint32_t cus = c->cus ? c->cus : 256u;
+    QZD_TRY(grow_dev(c, (void **)&c->d_lane, &c->lane_cap, (size_t)P.batch * P.chunk_b));
+    hipStream_t st = c->st[0];
+    return slot_rounds(c, nb, P.stride, P.batch, d_dst, dst_cap, h_out_len, h_frame_len, [&](uint32_t b, uint32_t bn, uint8_t *slots) -> int {
+        const uint64_t boff = (uint64_t)b * block_sz;
+        HIPCHK(c, hipMemsetAsync(c->k1_counter, 0, 4, st));
+        HIPCHK(c, hipMemset2DAsync(c->d_lane, P.chunk_b, 0, P.head_b, bn, st));        /* the head table is what a chunk's scratch begins with */
+        hipLaunchKernelGGL(qzk_zstd_chain_kernel, dim3(bn), dim3(64), 0, st, d_src + boff, n - boff, block_sz, bn, mini_match, c->d_lane);
+        hipLaunchKernelGGL(qzk_zstd_search_kernel, dim3(bn), dim3(64), 0, st, d_src + boff, n - boff, block_sz, bn, mini_match, parse_depth, c->d_lane);
+        hipLaunchKernelGGL(qzk_zstd_lazy_kernel, dim3(bn), dim3(64), 0, st, d_src + boff, n - boff, block_sz, bn, mini_match, parse_depth, c->d_lane);
+        const uint32_t waves = std::min<uint32_t>(bn, QZD_ZS_WPC * cus);
+        if (seq_flags)
+            hipLaunchKernelGGL(qzk_zstd_parse_encode_seq_kernel, dim3(waves), dim3(64), 0, st, d_src + boff, n - boff, block_sz, bn, slots,
+                               P.stride, c->d_len + b, c->k1_counter, c->d_lane, seq_flags);
+        else
+            hipLaunchKernelGGL(qzk_zstd_parse_encode_kernel, dim3(waves), dim3(64), 0, st, d_src + boff, n - boff, block_sz, bn, slots,
+                               P.stride, c->d_len + b, c->k1_counter, c->d_lane);
+        return QZD_OK;
+    });
 }
 
 extern "C" int qzd_zstd_encode_frames_ex(qzd_ctx *c, const uint8_t *d_literals, const uint32_t *d_seqs, const uint32_t *h_desc,

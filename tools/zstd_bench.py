@@ -12,7 +12,15 @@ repeated to the size of the buffer - the stage has no state across chunks, so eq
 handed to qzd_zstd_encode_frames; its frames must be the ones qzd_zstd_compress_frames wrote for those chunks.
 --seq-flags N (or a list, 0,1,2,3): every zstd line once per N through the _ex calls with those seq_flags
 (include/qzamd_zstd_seq.h: 1 FSE_Compressed tables, 2 repeat offsets) instead of once through the calls without.
-usage: zstd_bench.py [--mib 1024] [--calls 3] [--enc-mib 16] [--seq-flags N[,N...]]"""
+--parse-depth D (or a list, 4,16,64): behind every zstd line one line per D through qzd_zstd_compress_frames_parse
+(include/qzamd_zstd_parse.h: the hash-chain lazy parse with D search attempts per position), each followed by the default
+parse again, so that the two alternate in one process; --mm and --chunks narrow the configurations, --no-enc leaves the
+entropy stage alone out.
+--libzstd: where libzstd loads, its ZSTD_compress on --threads threads (default 16) of this box, every chunk alone, on the
+128 MiB the buffer is tiled from: ratio and rate per level 1 .. 19 and chunk size, then per Kzp line the lowest level whose
+output is no larger than that line's, with its rate.
+usage: zstd_bench.py [--mib 1024] [--calls 3] [--enc-mib 16] [--seq-flags N[,N...]] [--parse-depth D[,D...]] [--mm 3,4]
+                     [--chunks 65536,131072] [--no-enc] [--libzstd] [--threads 16]"""
 import argparse
 import os
 import sys
@@ -36,7 +44,14 @@ ap.add_argument("--mib", type=int, default=1024)
 ap.add_argument("--calls", type=int, default=3)
 ap.add_argument("--enc-mib", type=int, default=16)
 ap.add_argument("--seq-flags", default=None, help="seq_flags for the zstd calls, e.g. 3 or 0,1,2,3")
+ap.add_argument("--parse-depth", default=None, help="parse depths for qzd_zstd_compress_frames_parse, e.g. 16 or 4,16,64")
+ap.add_argument("--mm", default="3,4", help="the mini_match values to run")
+ap.add_argument("--chunks", default="65536,131072", help="the chunk sizes to run")
+ap.add_argument("--no-enc", action="store_true", help="skip the entropy stage alone")
+ap.add_argument("--libzstd", action="store_true", help="libzstd's ZSTD_compress on --threads threads beside the Kzp lines")
+ap.add_argument("--threads", type=int, default=16)
 args = ap.parse_args()
+DEPTHS = [] if args.parse_depth is None else [int(v) for v in args.parse_depth.split(",")]
 FLAGS = [None] if args.seq_flags is None else [int(v) for v in args.seq_flags.split(",")]
 n = args.mib << 20
 base = datagen.gen("silesia", min(128 << 20, n), 20250523)
@@ -64,22 +79,81 @@ def tag(fl):
     return "" if fl is None else ", seq_flags %d" % fl
 
 
-for hw in (65536, 131072):
-    for mm in (3, 4):
+KZP = []                            # (chunk size, line, ratio, GB/s) of every Kzp line
+
+
+def libzstd_leg():
+    """ZSTD_compress per chunk on args.threads threads (ctypes drops the GIL in the call): per chunk size the ratio and rate
+    of every level on `base`, then the lowest level that is no larger than each Kzp line"""
+    import ctypes as C
+    import time
+    from concurrent.futures import ThreadPoolExecutor
+    import zstd_ref
+    L = zstd_ref.lib()
+    if not L:
+        print("libzstd does not load here: no libzstd lines")
+        return
+    data = bytes(base)
+    buf = C.create_string_buffer(data, len(data))
+    addr, nt = C.addressof(buf), args.threads
+
+    def work(a):
+        lo, hi, hw, level = a
+        cap = L.ZSTD_compressBound(hw)
+        dst = C.create_string_buffer(cap)
+        return sum(L.ZSTD_compress(dst, cap, C.c_char_p(addr + off), min(hw, hi - off), level) for off in range(lo, hi, hw))
+
+    for hw in sorted(set(k[0] for k in KZP)) or [int(v) for v in args.chunks.split(",")]:
+        per = (len(data) // hw + nt - 1) // nt * hw
+        levels = {}
+        for level in range(1, 20):
+            t = time.time()
+            with ThreadPoolExecutor(nt) as ex:
+                tot = sum(ex.map(work, [(i, min(i + per, len(data)), hw, level) for i in range(0, len(data), per)]))
+            dt = time.time() - t
+            levels[level] = (tot / len(data), len(data) / dt / 1e9)
+            print("libzstd %d  %3d KB chunks, level %2d, %d threads      %8.2f GB/s   ratio %.4f" % (zstd_ref.version(), hw >> 10, level, nt, levels[level][1], levels[level][0]), flush=True)
+        for _, what, ratio, rate in (k for k in KZP if k[0] == hw):
+            ok = [lv for lv in sorted(levels) if levels[lv][0] <= ratio]
+            if ok:
+                r, g = levels[ok[0]]
+                print("    %s: %.2f GB/s at %.4f; libzstd's lowest level that is no larger: %d (%.4f) at %.2f GB/s on %d threads - %s" % (
+                    what, rate, ratio, ok[0], r, g, nt, "this writer is SLOWER" if rate < g else "this writer is %.1f times faster" % (rate / g)), flush=True)
+            else:
+                print("    %s: %.2f GB/s at %.4f; no libzstd level up to 19 is as small" % (what, rate, ratio), flush=True)
+
+
+def check_head(hw, full):
+    head = d_c.download(1 << 20).tobytes()
+    src_head = d_src.download(4 * hw).tobytes()
+    pos = 0
+    for k in range(4):
+        f, pos = zstd_full_format.decode_frame(head, pos) if full else zstd_format.decode_frame(head, pos)
+        assert f["data"] == src_head[k * hw:(k + 1) * hw]
+
+
+for hw in [int(v) for v in args.chunks.split(",")]:
+    for mm in [int(v) for v in args.mm.split(",")]:
         z_ms = []
         for fl in FLAGS:
-            _, ms = run("Kz  zstd  %3d KB chunks, mini_match %d%s" % (hw >> 10, mm, tag(fl)),
-                        lambda: ctx.zstd_compress_frames(d_src, n, d_c, hw, mm, 1, seq_flags=fl)[0])
+            default = lambda: ctx.zstd_compress_frames(d_src, n, d_c, hw, mm, 1, seq_flags=fl)[0]
+            _, ms = run("Kz  zstd  %3d KB chunks, mini_match %d%s" % (hw >> 10, mm, tag(fl)), default)
             z_ms.append(ms)
-            head = d_c.download(1 << 20).tobytes()
-            src_head = d_src.download(4 * hw).tobytes()
-            pos = 0
-            for k in range(4):
-                f, pos = zstd_full_format.decode_frame(head, pos) if fl else zstd_format.decode_frame(head, pos)
-                assert f["data"] == src_head[k * hw:(k + 1) * hw]
+            check_head(hw, fl)
+            for depth in DEPTHS:
+                what = "Kzp zstd  %3d KB chunks, mini_match %d%s, depth %d" % (hw >> 10, mm, tag(fl), depth)
+                out, ms = run(what, lambda: ctx.zstd_compress_frames(d_src, n, d_c, hw, mm, 1, seq_flags=fl, parse_depth=depth)[0])
+                KZP.append((hw, what, out / n, n / (ms * 1e-3) / 1e9))
+                check_head(hw, True)
+                run("Kz  zstd  %3d KB chunks, mini_match %d%s (again)" % (hw >> 10, mm, tag(fl)), default)
         _, l_ms = run("K4s LZ4s  %3d KB chunks, mini_match %d" % (hw >> 10, mm), lambda: ctx.lz4s_compress_blocks(d_src, n, d_c, hw, mm, 1)[0])
         print("    (the first 4 frames decode to their input; zstd call / LZ4s call = %s)" % " / ".join("%.2f" % (z / l_ms) for z in z_ms), flush=True)
 
+if args.libzstd:
+    libzstd_leg()
+if args.no_enc:
+    ctx.close()
+    sys.exit(0)
 # the entropy stage alone, 64 KB chunks, mini_match 3
 hw, mm = 65536, 3
 m = min(args.enc_mib << 20, n)
