@@ -332,7 +332,7 @@ int qzd_lz4_decode_route(qzd_ctx *ctx, int route);
  *   -2 the frame's output is beyond out_cap (known from Frame_Content_Size before a byte is written, else when it happens)
  *   -3 truncated: the input ends inside the frame
  *   -4 content checksum mismatch (the output has been written)
- *   -5 unsupported: a dictionary id, a content size above 32 bits
+ *   -5 unsupported: a dictionary id, a content size above 32 bits, a Window_Descriptor whose exponent passes 2^31
  * in_used / out_len of a failed frame are 0 (of a checksum mismatch: the frame's).  Nothing is loaded beyond a frame's in_len
  * or stored beyond its out_cap.  Two stages (qzk_zstdd.h): the bit streams, four frames a wave, into per-frame scratch
  * - about 5 bytes per byte of out_cap and 4 per byte of input - then the copy engine of the inflate, a wave per frame.  The

@@ -34,7 +34,7 @@
 #define QZK_ZD_EOUT (-2)            /* output beyond out_cap */
 #define QZK_ZD_ETRUNC (-3)          /* the input ends inside the frame */
 #define QZK_ZD_ECKSUM (-4)          /* content checksum mismatch */
-#define QZK_ZD_EUNSUP (-5)          /* a dictionary id; a content size above 32 bits */
+#define QZK_ZD_EUNSUP (-5)          /* a dictionary id; a content size above 32 bits; a window exponent above 31 */
 
 #define QZK_ZD_MAXBLK 131072u
 #define QZK_ZD_HUFLOG 11
@@ -251,6 +251,7 @@ QZ_DEV int qzk_zd_huf_plan(qzk_zd_frame *F, uint32_t nw)
     if (maxbits > QZK_ZD_HUFLOG) return QZK_ZD_EDATA;
     const uint32_t lw = 32u - (uint32_t)__builtin_clz(rest);
     F->w[nw] = (uint8_t)lw; F->rank[lw]++;
+    if (F->rank[1] < 2) return QZK_ZD_EDATA;                        /* no two symbols of weight 1: libzstd's HUF_readStats refuses it */
     uint32_t at = 0;
     for (uint32_t w = 1; w <= maxbits; w++) { const uint32_t c = F->rank[w]; F->rank[w] = at; at += c << (w - 1); }
     for (uint32_t s = 0; s <= nw; s++) {
@@ -296,6 +297,7 @@ QZ_DEV int qzk_zd_frame_header(qzk_zd_frame *F, const uint8_t *in, uint32_t in_l
     uint64_t window = 0;
     if (!single) {
         const uint32_t wlog = 10 + (in[p] >> 3);
+        if (wlog > 31) return QZK_ZD_EUNSUP;                        /* libzstd's ZSTD_WINDOWLOG_MAX: it refuses such a frame */
         window = (1ull << wlog) + ((1ull << wlog) >> 3) * (in[p] & 7u);
         p++;
     }

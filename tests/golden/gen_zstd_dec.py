@@ -256,6 +256,14 @@ def main():
              CAUSES["repeat_without_table"])
     explicit("huffman_code_above_11", hand_block(bytes.fromhex("42c00080c00100")), "hand-built: four Huffman literals, direct weights, one weight of 12", 64,
              CAUSES["huffman_code_above_11"])
+    # what the corruption sweep found (tests/test_sim_zstdd_corrupt.py): a direct weight of c_edge_two changed from 1 to 3, 5 or
+    # 9 - the implied symbol gets the same weight, two one-bit codes and no symbol of weight 1, which HUF_readStats refuses
+    with open(os.path.join(OUT, "c_edge_two.zst"), "rb") as f:
+        two = f.read()
+    assert two[17] == 0x01
+    for w in (3, 5, 9):
+        explicit("huffman_no_weight_1_w%d" % w, two[:17] + bytes([w]) + two[18:], "c_edge_two with byte 17, among its direct weights, 0x%02x instead of 0x01" % w,
+                 900, "without two symbols of weight 1")
     bases = [("a_text_3073_L1", small, 3073)]
     for e in list(entries):
         if e["name"] in ("c_edge_two", "c_edge_fibonacci", "c_edge_ml3", "c_edge_huf1024", "c_edge_count128", "b_text_70001_mm3_c1", "b_records_70001_mm4_c1"):

@@ -4,8 +4,10 @@
  * The launch sequence is the device layer's (qzd_zstdd.hip, qzd_zstd_decompress_frames): rounds of frames by
  * qzd_zstdd_host.h itself, then per round stage E, stage X and the checksum kernel.
  * With SIM_ZSTDD_MAIN the file is a program of its own: `sim_zstdd refuse FILE...` expects a non-zero status of every file,
- * `sim_zstdd cut FILE` decodes the frame whole and cut at every byte - each in an allocation of exactly its size, which is
- * what a build with -fsanitize=address,undefined checks the loads against.
+ * `sim_zstdd cut FILE` decodes the frame whole and cut at every byte, `sim_zstdd recipe BASE RECIPES OUT_CAP` decodes BASE once
+ * per line "position value" of RECIPES with that byte set to that value and prints "position value status in_used out_len"
+ * - each in an allocation of exactly its size, which is what a build with -fsanitize=address,undefined checks the loads
+ * against.
  */
 #define QZ_SIM 1
 #include "hipsim.h"
@@ -89,9 +91,30 @@ static int decode_prefix(const std::vector<uint8_t> &frame, size_t n, uint32_t o
 }
 int main(int argc, char **argv)
 {
-    if (argc < 3) { fprintf(stderr, "usage: sim_zstdd refuse|cut FILE...\n"); return 2; }
+    if (argc < 3) { fprintf(stderr, "usage: sim_zstdd refuse|cut FILE... | recipe BASE RECIPES OUT_CAP\n"); return 2; }
     const bool cut = !strcmp(argv[1], "cut");
     int fails = 0;
+    if (!strcmp(argv[1], "recipe")) {
+        if (argc != 5) { fprintf(stderr, "usage: sim_zstdd recipe BASE RECIPES OUT_CAP\n"); return 2; }
+        std::vector<uint8_t> frame = slurp(argv[2]);
+        const uint32_t cap = (uint32_t)strtoul(argv[4], NULL, 10);
+        FILE *f = fopen(argv[3], "r");
+        if (!f) { fprintf(stderr, "cannot open %s\n", argv[3]); return 2; }
+        unsigned long pos, value;
+        while (fscanf(f, "%lu %lu", &pos, &value) == 2) {
+            if (pos >= frame.size() || value > 255) { fprintf(stderr, "%s: byte %lu = %lu is outside the frame\n", argv[3], pos, value); fails++; continue; }
+            const uint8_t keep = frame[pos];
+            frame[pos] = (uint8_t)value;
+            qzk_zdres r;
+            const int rc = decode_prefix(frame, frame.size(), cap, &r);
+            frame[pos] = keep;
+            if (rc) { fprintf(stderr, "%s byte %lu = %lu: guard %d\n", argv[2], pos, value, rc); fails++; }
+            printf("%lu %lu %d %u %u\n", pos, value, r.status, r.in_used, r.out_len);
+        }
+        fclose(f);
+        printf("sim_zstdd: %d failures\n", fails);
+        return fails ? 1 : 0;
+    }
     for (int a = 2; a < argc; a++) {
         const std::vector<uint8_t> frame = slurp(argv[a]);
         uint64_t content = 0, bound = 0; bool hc = false;

@@ -53,20 +53,25 @@ class BackBits:
     def __init__(self, data):
         if len(data) == 0 or data[-1] == 0:
             raise FormatError("a stream without its end mark")
-        self.v = int.from_bytes(data, "little")
-        self.n = self.v.bit_length() - 1
+        self.d = bytes(data)
+        self.n = 8 * (len(data) - 1) + data[-1].bit_length() - 1       # the bits below the end mark
+
+    def _bits(self, hi, k):
+        """bits hi - k .. hi - 1 of the stream as a little-endian number (a window of bytes: a long stream costs no more)"""
+        lo = hi - k
+        return (int.from_bytes(self.d[lo >> 3:(hi + 7) >> 3], "little") >> (lo & 7)) & ((1 << k) - 1)
 
     def read(self, k):
         if k > self.n:
             raise FormatError("a stream is read past its beginning")
         self.n -= k
-        return (self.v >> self.n) & ((1 << k) - 1)
+        return self._bits(self.n + k, k)
 
     def peek_padded(self, k):
         """the next k bits, zeros where the stream has no more"""
         if k <= self.n:
-            return (self.v >> (self.n - k)) & ((1 << k) - 1)
-        return (self.v & ((1 << self.n) - 1)) << (k - self.n)
+            return self._bits(self.n, k)
+        return self._bits(self.n, self.n) << (k - self.n)
 
     def done(self):
         if self.n:
@@ -109,8 +114,8 @@ OF_TABLE = fse_table(OF_NORM, 5)
 ML_TABLE = fse_table(ML_NORM, 6)
 
 
-def read_ncount(data, max_log, max_symbols):
-    """an FSE table description -> (distribution, accuracy log, bytes used)"""
+def read_ncount(data, max_log, max_symbols, notes=None):
+    """an FSE table description -> (distribution, accuracy log, bytes used); notes (a set) <- "ncount:..." tags of its shape"""
     v = int.from_bytes(data, "little")
     avail = 8 * len(data)
     log = 5 + (v & 15)
@@ -121,12 +126,16 @@ def read_ncount(data, max_log, max_symbols):
     norm, prev0 = [], False
     while remaining > 1:
         if prev0:
+            run = 1
             while True:
                 r = (v >> pos) & 3
                 pos += 2
                 norm += [0] * r
+                run += r
                 if r != 3:
                     break
+            if notes is not None:
+                notes.add("ncount:zrun:%d" % run)
         if len(norm) >= max_symbols:
             raise FormatError("a distribution with more than %d symbols" % max_symbols)
         mx = (2 * threshold - 1) - remaining
@@ -149,12 +158,18 @@ def read_ncount(data, max_log, max_symbols):
             threshold >>= 1
         if pos > avail:
             raise FormatError("a distribution is cut by its field's end")
+    if notes is not None:
+        notes.add("ncount:lastbits:%d" % ((pos - 1) % 8 + 1))
+        if -1 in norm:
+            notes.add("ncount:lessthan1")
     return norm, log, (pos + 7) // 8
 
 
-def read_weights_fse(data):
+def read_weights_fse(data, notes=None):
     """FSE-compressed Huffman weights (4.2.1.2): two states taking turns until the stream is used up"""
-    norm, log, used = read_ncount(data, 6, 13)
+    norm, log, used = read_ncount(data, 6, 13, notes)
+    if notes is not None:
+        notes.add("wlog:%d" % log)
     table = fse_table(norm, log)
     bits = BackBits(data[used:])
     st = [bits.read(log), bits.read(log)]
@@ -171,6 +186,8 @@ def read_weights_fse(data):
         k ^= 1
         if len(out) > 255:
             raise FormatError("more than 255 weights")
+    if len(out) > 255:                                              # (the last two come without another look at the count)
+        raise FormatError("more than 255 weights")
     bits.done()
     return out
 
@@ -189,6 +206,8 @@ def huffman_table(weights):
     weights = list(weights) + [rest.bit_length()]
     if any(w > maxbits for w in weights):
         raise FormatError("a Huffman weight above the tree's height")
+    if weights.count(1) < 2:                                        # libzstd's HUF_readStats: rankStats[1] < 2
+        raise FormatError("a Huffman tree without two symbols of weight 1")
     table = []
     for w in range(1, maxbits + 1):
         for s, ws in enumerate(weights):

@@ -66,13 +66,18 @@ class _Frame:
         self.tabs = {"LL": None, "OF": None, "ML": None}
         self.rep = [1, 4, 8]
         self.tally = set()
+        self.sections = []                 # (name, start, end) in the frame's bytes
+        self.lit_types = []                # the literals type of every Compressed block so far
+        self.tkind = {"LL": None, "OF": None, "ML": None}     # what each table was last set from
+        self.nseq0_since = {"LL": False, "OF": False, "ML": False}
 
 
-def _literals(blk, F):
-    """-> (literals, bytes used)"""
+def _literals(blk, F, at=0):
+    """-> (literals, bytes used); at: where blk begins in the frame (for the sections)"""
     if not blk:
         raise FormatError("a block without a literals section")
     t, fmt = blk[0] & 3, (blk[0] >> 2) & 3
+    F.lit_types.append(("raw", "rle", "huffman", "treeless")[t])
     if t < 2:
         hs = 1 if not fmt & 1 else 2 if fmt == 1 else 3
         if len(blk) < hs:
@@ -84,10 +89,12 @@ def _literals(blk, F):
             if len(blk) < hs + n:
                 raise FormatError("raw literals are cut by the block's end")
             F.tally.add("lit:raw")
+            F.sections += [("literals_header", at, at + hs), ("raw_literals", at + hs, at + hs + n)]
             return bytes(blk[hs:hs + n]), hs + n
         if len(blk) < hs + 1:
             raise FormatError("the RLE literal is missing")
         F.tally.add("lit:rle")
+        F.sections += [("literals_header", at, at + hs), ("rle_literal", at + hs, at + hs + 1)]
         return bytes(blk[hs:hs + 1]) * n, hs + 1
     hs, bits, streams = ((3, 10, 1), (3, 10, 4), (4, 14, 4), (5, 18, 4))[fmt]
     if len(blk) < hs:
@@ -99,10 +106,14 @@ def _literals(blk, F):
     if len(blk) < hs + csz:
         raise FormatError("compressed literals are cut by the block's end")
     body = blk[hs:hs + csz]
+    F.sections.append(("literals_header", at, at + hs))
+    at += hs
     if t == 3:
         if F.huf is None:
             raise FormatError("treeless literals without a previous tree")
         F.tally.add("lit:treeless")
+        if F.lit_types[-3:] == ["huffman", "raw", "treeless"]:
+            F.tally.add("lit:treeless<raw<huffman")
         dsz = 0
     else:
         if not body:
@@ -115,19 +126,27 @@ def _literals(blk, F):
                 raise FormatError("the weights are cut")
             weights = [(body[1 + i // 2] >> 4) if i % 2 == 0 else (body[1 + i // 2] & 15) for i in range(nw)]
             F.tally.add("weights:direct")
+            if nw == 128:
+                F.tally.add("weights:direct128")
+            F.sections += [("tree_header", at, at + 1), ("tree_weights", at + 1, at + dsz)]
         else:
             if hb == 0 or len(body) < 1 + hb:
                 raise FormatError("the compressed weights are cut")
-            weights = read_weights_fse(body[1:1 + hb])
+            weights = read_weights_fse(body[1:1 + hb], F.tally)
             dsz = 1 + hb
+            F.sections += [("tree_header", at, at + 1), ("tree_weights", at + 1, at + dsz)]
             F.tally.add("weights:fse")
         F.huf = huffman_table(weights)
         F.tally.add("lit:huffman")
     table, maxbits = F.huf
     F.tally.add("hufbits:%d" % maxbits)
     rest = body[dsz:]
+    at += dsz
     if streams == 1:
         lits = huffman_stream(rest, table, maxbits, n)
+        F.sections.append(("stream1", at, at + len(rest)))
+        if n == 1:
+            F.tally.add("lit:1stream:1")
     else:
         F.tally.add("lit:4streams%d" % bits)
         if len(rest) < 6:
@@ -141,6 +160,10 @@ def _literals(blk, F):
             raise FormatError("%d literals in four streams" % n)
         cuts = [0, s1, s1 + s2, s1 + s2 + s3, len(rest)]
         counts = [seg, seg, seg, n - 3 * seg]
+        if counts[3] < 2:
+            F.tally.add("lit:stream4:%d" % counts[3])
+        F.sections.append(("jump_table", at, at + 6))
+        F.sections += [("stream%d" % (i + 1), at + 6 + cuts[i], at + 6 + cuts[i + 1]) for i in range(4)]
         lits = b"".join(huffman_stream(rest[cuts[i]:cuts[i + 1]], table, maxbits, counts[i]) for i in range(4))
     return lits, hs + csz
 
@@ -148,9 +171,16 @@ def _literals(blk, F):
 _SEQ = {"LL": (LL_TABLE, 6, 35, 9), "OF": (OF_TABLE, 5, 31, 8), "ML": (ML_TABLE, 6, 52, 9)}
 
 
-def _seq_table(mode, name, blk, pos, F):
+def _seq_table(mode, name, blk, pos, F, at):
     predefined, plog, maxcode, maxlog = _SEQ[name]
     F.tally.add("%s:%s" % (name.lower(), MODE_NAMES[mode]))
+    start = pos
+    if mode == 3:
+        if F.tabs[name] is not None and F.nseq0_since[name]:
+            F.tally.add("repeat<nseq0<%s" % F.tkind[name])
+    else:
+        F.tkind[name] = MODE_NAMES[mode]
+    F.nseq0_since[name] = False
     if mode == 0:
         F.tabs[name] = (predefined, plog)
     elif mode == 1:
@@ -161,16 +191,19 @@ def _seq_table(mode, name, blk, pos, F):
         F.tabs[name] = ([(blk[pos], 0, 0)], 0)
         pos += 1
     elif mode == 2:
-        norm, log, used = read_ncount(blk[pos:], maxlog, maxcode + 1)
+        norm, log, used = read_ncount(blk[pos:], maxlog, maxcode + 1, F.tally)
         F.tabs[name] = (fse_table(norm, log), log)
+        F.tally.add("tablelog:%s:%d" % (name.lower(), log))
         pos += used
     elif F.tabs[name] is None:
         raise FormatError("%s repeats a table that was never set" % name)
+    if pos > start:
+        F.sections.append(("%s_%s" % (name.lower(), "rle_code" if mode == 1 else "description"), at + start, at + pos))
     return pos
 
 
-def _sequences(blk, F, produced, nlits):
-    """-> [(literal length, match length, distance)], repeat offsets resolved"""
+def _sequences(blk, F, produced, nlits, at=0):
+    """-> [(literal length, match length, distance)], repeat offsets resolved; at: where blk begins in the frame"""
     if not blk:
         raise FormatError("a block without a sequences section")
     b0 = blk[0]
@@ -188,10 +221,14 @@ def _sequences(blk, F, produced, nlits):
         if len(blk) != 1:
             raise FormatError("bytes behind an empty sequences section")
         F.tally.add("nseq0")
+        F.sections.append(("sequence_count", at, at + 1))
+        for k in F.nseq0_since:
+            F.nseq0_since[k] = True
         return []
     if pos >= len(blk):
         raise FormatError("the modes byte is missing")
     modes = blk[pos]
+    F.sections += [("sequence_count", at, at + pos), ("modes", at + pos, at + pos + 1)]
     pos += 1
     if modes & 3:
         raise FormatError("reserved bits in the modes byte")
@@ -199,8 +236,9 @@ def _sequences(blk, F, produced, nlits):
     for shift, name in ((6, "LL"), (4, "OF"), (2, "ML")):
         if (modes >> shift) & 3 == 3 and not had:
             raise FormatError("%s repeats a table that was never set" % name)
-        pos = _seq_table((modes >> shift) & 3, name, blk, pos, F)
+        pos = _seq_table((modes >> shift) & 3, name, blk, pos, F, at)
     (llt, lllog), (oft, oflog), (mlt, mllog) = F.tabs["LL"], F.tabs["OF"], F.tabs["ML"]
+    F.sections.append(("bitstream", at + pos, at + len(blk)))
     bits = BackBits(blk[pos:])
     sl, so, sm = bits.read(lllog), bits.read(oflog), bits.read(mllog)
     seqs, rep, used = [], F.rep, 0
@@ -234,6 +272,10 @@ def _sequences(blk, F, produced, nlits):
         produced += ll
         if off > produced:
             raise FormatError("offset %d with %d bytes produced" % (off, produced))
+        if off == produced:
+            F.tally.add("offset:all-produced")
+        if i == 0 and (ll, ml, off) == (1, 3, 1):
+            F.tally.add("seq0:ll1:ml3:off1")
         produced += ml
         seqs.append((ll, ml, off))
         if i + 1 < n:
@@ -263,6 +305,8 @@ def frame_header(buf, pos=0):
     window = None
     if not single:
         wlog = 10 + (buf[p] >> 3)
+        if wlog > 31:                                               # libzstd's ZSTD_WINDOWLOG_MAX
+            raise FormatError("a window log of %d" % wlog)
         window = (1 << wlog) + ((1 << wlog) >> 3) * (buf[p] & 7)
         p += 1
     content = None
@@ -273,8 +317,16 @@ def frame_header(buf, pos=0):
 
 def decode_frame(buf, pos=0):
     """the frame at buf[pos:] -> (info, where the next one begins).  info: "data", "size", "content_size" (or None), "blocks",
-    "tally" (a sorted list), "skippable" """
-    buf = bytes(buf)
+    "tally" (a sorted list), "skippable", "sections" ([(name, start, end)] in the order met, positions from the frame's start) """
+    F = _Frame()
+    try:
+        return _decode_frame(bytes(buf), pos, F)
+    except FormatError as e:
+        e.sections = F.sections             # what was read before the refusal
+        raise
+
+
+def _decode_frame(buf, pos, F):
     start = pos
     if len(buf) - pos < 4:
         raise Truncated("no magic")
@@ -285,11 +337,11 @@ def decode_frame(buf, pos=0):
         sz = int.from_bytes(buf[pos + 4:pos + 8], "little")
         if len(buf) - pos < 8 + sz:
             raise Truncated("a skippable frame is cut")
-        return {"data": b"", "size": 8 + sz, "content_size": 0, "blocks": 0, "tally": ["skippable"], "skippable": True}, pos + 8 + sz
+        return {"data": b"", "size": 8 + sz, "content_size": 0, "blocks": 0, "tally": ["skippable"], "skippable": True,
+                "sections": [("frame_header", 0, 8), ("skippable_data", 8, 8 + sz)]}, pos + 8 + sz
     if magic != MAGIC:
         raise FormatError("no zstd magic")
     h = frame_header(buf, pos)
-    F = _Frame()
     F.tally.add("fcs:%d" % h["fcs_bytes"])
     F.tally.add("single" if h["single"] else "window")
     if h["window"] is not None and h["content_size"] is not None:
@@ -298,6 +350,11 @@ def decode_frame(buf, pos=0):
         F.tally.add("checksum")
     window = h["window"] if h["window"] is not None else h["content_size"]
     bmax = min(window, MAX_BLOCK)
+    if not h["single"] and buf[pos + 5] & 7:
+        F.tally.add("window:mantissa")
+    if h["content_size"] in (255, 256, 65791, 65792):
+        F.tally.add("content:%d" % h["content_size"])
+    F.sections.append(("frame_header", 0, h["header_size"]))
     pos += h["header_size"]
     out = bytearray()
     nblocks = 0
@@ -308,6 +365,7 @@ def decode_frame(buf, pos=0):
         pos += 3
         last, btype, bsz = bh & 1, (bh >> 1) & 3, bh >> 3
         nblocks += 1
+        F.sections.append(("block_header", pos - 3 - start, pos - start))
         if btype == 3:
             raise FormatError("block type 3")
         if bsz > bmax:
@@ -316,23 +374,31 @@ def decode_frame(buf, pos=0):
             if len(buf) - pos < bsz:
                 raise Truncated("a Raw block is cut")
             out += buf[pos:pos + bsz]
+            F.sections.append(("raw_block", pos - start, pos - start + bsz))
             pos += bsz
             F.tally.add("block:raw")
+            if last and bsz == 0:
+                F.tally.add("block:raw:empty-last")
+            if h["window"] is not None and bsz == bmax < MAX_BLOCK:
+                F.tally.add("block:at-window")
         elif btype == 1:
             if len(buf) - pos < 1:
                 raise Truncated("an RLE block is cut")
             out += buf[pos:pos + 1] * bsz
+            F.sections.append(("rle_block", pos - start, pos - start + 1))
             pos += 1
             F.tally.add("block:rle")
+            if bsz in (1, MAX_BLOCK):
+                F.tally.add("block:rle:%s" % ("1" if bsz == 1 else "max"))
         else:
             if len(buf) - pos < bsz:
                 raise Truncated("a Compressed block is cut")
             blk = buf[pos:pos + bsz]
             pos += bsz
             F.tally.add("block:compressed")
-            lits, used = _literals(blk, F)
+            lits, used = _literals(blk, F, pos - bsz - start)
             before = len(out)
-            seqs = _sequences(blk[used:], F, before, len(lits))
+            seqs = _sequences(blk[used:], F, before, len(lits), pos - bsz - start + used)
             lp = 0
             for ll, ml, off in seqs:
                 out += lits[lp:lp + ll]
@@ -345,6 +411,8 @@ def decode_frame(buf, pos=0):
             out += lits[lp:]
             if len(out) - before > bmax:
                 raise FormatError("a block of %d bytes with a maximum of %d" % (len(out) - before, bmax))
+            if len(out) - before == MAX_BLOCK:
+                F.tally.add("block:compressed:max")
         if h["content_size"] is not None and len(out) > h["content_size"]:
             raise FormatError("output beyond the content size")
         if last:
@@ -356,9 +424,10 @@ def decode_frame(buf, pos=0):
             raise Truncated("the content checksum is cut")
         if int.from_bytes(buf[pos:pos + 4], "little") != xxh64(bytes(out)) & 0xFFFFFFFF:
             raise FormatError("content checksum mismatch")
+        F.sections.append(("checksum", pos - start, pos - start + 4))
         pos += 4
     return {"data": bytes(out), "size": pos - start, "content_size": h["content_size"], "blocks": nblocks,
-            "tally": sorted(F.tally), "skippable": False}, pos
+            "tally": sorted(F.tally), "skippable": False, "sections": F.sections}, pos
 
 
 def decode_frames(stream):
