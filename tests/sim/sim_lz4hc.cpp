@@ -64,3 +64,39 @@ uint32_t sim_lz4hc_block(const uint8_t *src, uint64_t total, uint32_t frame_sz, 
 uint32_t sim_lz4hc_stride(void) { return hc_stride(); }
 
 }
+
+#ifdef SIM_LZ4HC_MAIN
+/* A program of its own for the sanitizers (tests/test_sim_lz4hc_traps.py builds it with -fsanitize=address,undefined):
+ * reads inputs (u32le length + bytes, one after the other) from the file named on its command line, puts each into a heap
+ * buffer of EXACTLY its length and runs level 3 in rounds of one block and level 8 in one round on it.  A search, a count or
+ * a chain trip that reads past an input's end stops it: that is what this program is for.  Of the bytes it checks only that
+ * a frame came out; the comparison with liblz4's pinned bytes is the test's. */
+#include <cstdio>
+#include <cstdlib>
+int main(int argc, char **argv)
+{
+    if (argc < 2) return 2;
+    FILE *f = fopen(argv[1], "rb");
+    if (!f) return 2;
+    unsigned count = 0, failures = 0;
+    uint8_t lenb[4];
+    while (fread(lenb, 1, 4, f) == 4) {
+        const uint32_t n = lenb[0] | lenb[1] << 8 | lenb[2] << 16 | (uint32_t)lenb[3] << 24;
+        uint8_t *src = (uint8_t *)malloc(n ? n : 1);
+        if (n && fread(src, 1, n, f) != n) return 2;
+        const uint64_t cap = (uint64_t)n + 64 + 32 * (n / QZK_LZ4_MAXBLK + 3);
+        for (int level = 3; level <= 8; level += 5) {
+            uint8_t *a = (uint8_t *)malloc(cap);
+            uint64_t la = 0;
+            const int ra = sim_lz4hc(src, n, n ? n : 1, level, 0, level == 3 ? 1 : 0, a, cap, &la, NULL);
+            if (ra || la < 11 || la > cap) { failures++; printf("input %u (n = %u) level %d: %d, %llu bytes\n", count, n, level, ra, (unsigned long long)la); }
+            free(a);
+        }
+        free(src);
+        count++;
+    }
+    fclose(f);
+    printf("%u inputs, %u failures\n", count, failures);
+    return failures ? 1 : 0;
+}
+#endif
