@@ -43,7 +43,8 @@
  * (Kzp).
  *
  * Scratch of a chunk (qzk_zp_carve; the host plan is qzd_zstd_parse_host.h): head table, chain distances (32 bits: a
- * distance reaches 131071), results (2 x 32 bits), literals, records, and 16 bytes for the two counts.
+ * distance reaches 131072 - mini_match, from the last position with mini_match bytes behind it to the chunk's first; a
+ * length 131071), results (2 x 32 bits), literals, records, and 16 bytes for the two counts.
  * No wave waits for another; every loop is bounded by depth or by the chunk's length.
  */
 #ifndef QZK_ZSTD_PARSE_H

@@ -144,6 +144,32 @@ int main()
     run("depth 257", text, 65536, 3, 3, 257, 0, -2);
     run("flags 4", text, 65536, 3, 4, 16, 0, -2);
     run("chunk 512", text, 512, 3, 3, 16, 0, -2);
+    /* corners of P3 and of a chunk's ends, planted as tests/zstd_parse_traps.py plants them, each in a buffer of exactly its
+     * size: the backward extension that stops at p == off (the chunk's first 20 bytes twice), rep1 - 1 == 0 (a run of one
+     * byte and a copy at once behind it), a copy with one byte dropped (rep1 - 1 taken), the last mini_match bytes a match,
+     * and chunks of 1 .. 4 bytes */
+    std::vector<uint8_t> twice(1024), runcopy(1024), dropped(1024), late(1024);
+    for (auto *v : { &twice, &runcopy, &dropped, &late }) for (auto &b : *v) { x = x * 1664525u + 1013904223u; b = (uint8_t)(x >> 24); }
+    for (size_t i = 0; i < 20; i++) twice[20 + i] = twice[i];
+    twice[40] = twice[0] ^ 0x55;
+    for (size_t i = 600; i < 640; i++) runcopy[i] = runcopy[600];
+    runcopy[599] = runcopy[600] ^ 0x55;
+    for (size_t i = 0; i < 12; i++) runcopy[640 + i] = runcopy[100 + i];
+    for (size_t i = 0; i < 20; i++) dropped[600 + i] = dropped[100 + i];
+    for (size_t i = 0; i < 19; i++) dropped[620 + i] = dropped[121 + i];
+    for (size_t i = 0; i < 4; i++) late[1020 + i] = late[1015 + i];
+    for (uint32_t mm = 3; mm <= 4; mm++)
+        for (uint32_t depth : { 1u, 16u, 64u }) {
+            run("first bytes twice", twice, 1024, mm, 3, depth, 0, 0);
+            run("run and copy", runcopy, 1024, mm, 3, depth, 0, 0);
+            run("byte dropped", dropped, 1024, mm, 3, depth, 0, 0);
+            run("late match", late, 1024, mm, 3, depth, 0, 0);
+            for (size_t n = 1; n <= 4; n++) {
+                run("short chunk", std::vector<uint8_t>(n, (uint8_t)7), 1024, mm, depth == 16 ? 0 : 3, depth, 0, 0);
+                std::vector<uint8_t> two(twice); two.insert(two.end(), runcopy.begin(), runcopy.begin() + n);
+                run("short last chunk", two, 1024, mm, 3, depth, 1, 0);
+            }
+        }
     /* the plan: a round never passes its budget nor QZD_ZP_ROUND chunks, and always holds one */
     for (uint32_t bs = 1024; bs <= 131072; bs *= 2)
         for (uint32_t nc : { 1u, 2u, 4095u, 4096u, 4097u, 1000000u }) {

@@ -9,6 +9,7 @@ import subprocess
 import pytest
 
 import zstd_parse_sim as P
+import zstd_parse_traps as T
 import zstd_seq_sim as Q
 import zstd_sim as S
 
@@ -64,7 +65,16 @@ def test_search_is_the_longest_match(name, mm):
     assert len(b) == 4096
     chain, res = P.search(b, 4096, mm, 256)
     want = P.brute_longest(b, mm)
-    # the chain: every link points at an earlier position of the chunk with the same mm bytes or a colliding hash
+    # the chain: every link points at the nearest earlier position of the chunk with the same hash of mm bytes (the serial
+    # model's P1, tests/zstd_parse_traps.py), at this head-table width and at the widest
+    assert chain == T.p1_chain(b, 4096, mm)
+    wide, wres = P.search(b, 131072, mm, 256)
+    assert wide == T.p1_chain(b, 131072, mm)
+    whops = [0] * len(b)
+    for p, d in enumerate(wide):
+        assert 0 <= d <= p and (d == 0 or d >= chain[p] > 0)       # fewer collisions: never nearer than the narrow table's
+        whops[p] = whops[p - d] + 1 if d else 0
+    assert all(wres[p] == want[p] for p in range(len(b)) if whops[p] <= 256)
     hops = [0] * len(b)
     for p, d in enumerate(chain):
         assert 0 <= d <= p

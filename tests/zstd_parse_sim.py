@@ -31,17 +31,22 @@ def build_so():
     return SO
 
 
+def load(path):
+    """the emulator library at `path` with its argument types (a build of SRC with other -D values: a mutant)"""
+    L = C.CDLL(path)
+    L.sim_zstd_parse.argtypes = [C.c_char_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                 C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sim_zstd_parse_round.argtypes = [C.c_uint32, C.c_uint32]
+    L.sim_zstd_parse_round.restype = C.c_uint32
+    L.sim_zstd_parse_chunk_bytes.argtypes = [C.c_uint32]
+    L.sim_zstd_parse_chunk_bytes.restype = C.c_uint64
+    return L
+
+
 def _load():
     global _S
     if _S is None:
-        L = C.CDLL(build_so())
-        L.sim_zstd_parse.argtypes = [C.c_char_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
-                                     C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.sim_zstd_parse_round.argtypes = [C.c_uint32, C.c_uint32]
-        L.sim_zstd_parse_round.restype = C.c_uint32
-        L.sim_zstd_parse_chunk_bytes.argtypes = [C.c_uint32]
-        L.sim_zstd_parse_chunk_bytes.restype = C.c_uint64
-        _S = L
+        _S = load(build_so())
     return _S
 
 
@@ -54,9 +59,10 @@ def chunk_bytes(hw_buff_sz):
     return _load().sim_zstd_parse_chunk_bytes(hw_buff_sz)
 
 
-def run(src, hw_buff_sz=65536, mini_match=3, flags=3, depth=16, round_cap=0, peek=False, records=False):
-    """-> (rc, stream, per-frame lengths, extras); extras: "chain", "res" (peek) and "seqs", "lits" (records), one chunk only"""
-    L = _load()
+def run(src, hw_buff_sz=65536, mini_match=3, flags=3, depth=16, round_cap=0, peek=False, records=False, lib=None):
+    """-> (rc, stream, per-frame lengths, extras); extras: "chain", "res" (peek) and "seqs", "lits" (records), one chunk only.
+    lib: a library from load(), the suite's own build otherwise"""
+    L = lib or _load()
     n = len(src)
     nb = (n + hw_buff_sz - 1) // hw_buff_sz
     cap = zstd_format.bound(n, hw_buff_sz)
@@ -86,16 +92,16 @@ def compress(src, hw_buff_sz=65536, mini_match=3, flags=3, depth=16, round_cap=0
     return stream, lens
 
 
-def records(chunk, hw_buff_sz, mini_match=3, depth=16, flags=3):
+def records(chunk, hw_buff_sz, mini_match=3, depth=16, flags=3, lib=None):
     """one chunk -> (its frame, [(ll, ml, off)], the literals)"""
-    rc, stream, _, x = run(chunk, hw_buff_sz, mini_match, flags, depth, records=True)
+    rc, stream, _, x = run(chunk, hw_buff_sz, mini_match, flags, depth, records=True, lib=lib)
     assert rc == 0
     return stream, x["seqs"], x["lits"]
 
 
-def search(chunk, hw_buff_sz, mini_match, depth):
+def search(chunk, hw_buff_sz, mini_match, depth, lib=None):
     """one chunk -> (chain distances, [(length, distance)] per position)"""
-    rc, _, _, x = run(chunk, hw_buff_sz, mini_match, 0, depth, peek=True)
+    rc, _, _, x = run(chunk, hw_buff_sz, mini_match, 0, depth, peek=True, lib=lib)
     assert rc == 0
     return x["chain"], x["res"]
 
