@@ -80,6 +80,10 @@ def load(build_if_missing=True):
     L.qzd_zstd_encode_frames_ex.argtypes = L.qzd_zstd_encode_frames.argtypes + [C.c_uint32]
     L.qzd_zstd_compress_frames_parse.argtypes = L.qzd_zstd_compress_frames.argtypes + [C.c_uint32, C.c_uint32]
     L.qzd_zstd_decompress_frames.argtypes = [vp, u8p, u8p, vp, C.c_uint32, vp]
+    if hasattr(L, "qzd_zstd_decompress_frames_ex"):         # (variant libraries built from older sources lack them)
+        L.qzd_zstd_decompress_frames_ex.argtypes = [vp, u8p, u8p, vp, C.c_uint32, vp, vp]
+        L.qzd_zstd_count_blocks.argtypes = [vp, u8p, vp, C.c_uint32, vp]
+        L.qzd_zstd_decode_route.argtypes = [vp, C.c_int]
     L.qzd_chunk_lens.argtypes = [vp, vp, C.c_uint32]
     L.qzd_shard_root_create.argtypes = [vp, C.c_uint32, C.c_uint64, C.c_char_p, C.POINTER(vp)]
     L.qzd_shard_attach.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_char_p, C.c_uint64, C.POINTER(vp)]
@@ -130,6 +134,7 @@ def exported_symbols():
             "qzd_lz4hc_compress_frames", "qzd_lz4hc_compress_frames_hw", "qzd_lz4hc_compress_linked",
             "qzd_lz4s_bound", "qzd_lz4s_compress_blocks",
             "qzd_zstd_bound", "qzd_zstd_compress_frames", "qzd_zstd_encode_frames", "qzd_zstd_decompress_frames",
+            "qzd_zstd_decompress_frames_ex", "qzd_zstd_count_blocks", "qzd_zstd_decode_route",
             "qzd_zstd_compress_frames_ex", "qzd_zstd_encode_frames_ex", "qzd_zstd_compress_frames_parse",
             "qzd_crcn_ranges", "qzd_xxh32_ranges", "qzd_blocks_compress", "qzd_blocks_decompress",
             "qzd_crc32_fold", "qzd_pcie_peak", "qzd_rccl_unique_id", "qzd_rccl_create", "qzd_rccl_gather", "qzd_rccl_close"]
@@ -381,13 +386,37 @@ class Context:
         self._chk(self.L.qzd_lz4_decompress_frames(self.h, d_comp.ptr, d_out.ptr, sa.ctypes.data, len(segs), res.ctypes.data))
         return res
 
-    def zstd_decompress_frames(self, d_comp, d_out, segs):
+    ZSTDD_ROUTES = {"auto": 0, "frame": 1, "blocks": 2}
+
+    def zstd_decode_route(self, route):
+        """which frames zstd_decompress_frames reads a block per lane group when their block counts are given: "auto" (2
+        blocks and more), "frame" (none) or "blocks" (every frame with a count)"""
+        self._chk(self.L.qzd_zstd_decode_route(self.h, self.ZSTDD_ROUTES[route]))
+
+    def zstd_decompress_frames(self, d_comp, d_out, segs, nblocks=None, route=None):
         """zstd and skippable frames; segs: list of (in_off, out_off, in_len, out_cap) -> structured results (status,
-        in_used, out_len): 0, or -1 malformed, -2 beyond out_cap, -3 truncated, -4 content checksum, -5 unsupported"""
+        in_used, out_len): 0, or -1 malformed, -2 beyond out_cap, -3 truncated, -4 content checksum, -5 unsupported.
+        nblocks: per frame its block count or 0 (qzd_zstd_decompress_frames_ex; -6 for a frame whose count is wrong);
+        route: see zstd_decode_route; given here it holds for this call and for those after it"""
+        if route is not None:
+            self.zstd_decode_route(route)
         sa = np.array([tuple(s) for s in segs], dtype=LZ4SEG_DT)
         res = np.zeros(len(segs), LZ4RES_DT)
-        self._chk(self.L.qzd_zstd_decompress_frames(self.h, d_comp.ptr, d_out.ptr, sa.ctypes.data, len(segs), res.ctypes.data))
+        if nblocks is None:
+            self._chk(self.L.qzd_zstd_decompress_frames(self.h, d_comp.ptr, d_out.ptr, sa.ctypes.data, len(segs), res.ctypes.data))
+        else:
+            nb = np.ascontiguousarray(nblocks, dtype=np.uint32)
+            assert len(nb) == len(segs)
+            self._chk(self.L.qzd_zstd_decompress_frames_ex(self.h, d_comp.ptr, d_out.ptr, sa.ctypes.data, len(segs), res.ctypes.data,
+                                                           nb.ctypes.data))
         return res
+
+    def zstd_count_blocks(self, d_comp, segs):
+        """the block counts of resident frames, 0 where a frame has no last block (qzd_zstd_count_blocks)"""
+        sa = np.array([tuple(s) for s in segs], dtype=LZ4SEG_DT)
+        nb = np.zeros(max(len(segs), 1), np.uint32)
+        self._chk(self.L.qzd_zstd_count_blocks(self.h, d_comp.ptr, sa.ctypes.data, len(segs), nb.ctypes.data))
+        return nb[:len(segs)]
 
     def inflate_timing(self):
         ms = (C.c_float * 4)()

@@ -143,6 +143,8 @@ def lib():
         L.qzSetSessionCrc32Config.argtypes = [P(QzSession), P(QzCrc32Config)]
         L.qzSetSessionZstdSeqAMD.argtypes = [P(QzSession), C.c_uint]
         L.qzSetSessionZstdParseAMD.argtypes = [P(QzSession), C.c_uint]
+        if hasattr(L, "qzSetSessionZstdDecodeRouteAMD"):
+            L.qzSetSessionZstdDecodeRouteAMD.argtypes = [P(QzSession), C.c_int]
         _bound = True
     return L
 
@@ -298,6 +300,13 @@ class Session:
         """qzSetSessionZstdParseAMD (include/qzamd_zstd_parse.h): 0 the default parse, 1 .. 256 the search attempts per position
         of the hash-chain lazy parse"""
         return self.L.qzSetSessionZstdParseAMD(C.byref(self.s), depth)
+
+    ZSTDD_ROUTES = {"auto": 0, "frame": 1, "blocks": 2}
+
+    def zstd_decode_route(self, route):
+        """qzSetSessionZstdDecodeRouteAMD (include/qzamd_zstd_blocks.h): "auto", "frame" or "blocks" for the qzDecompress calls of
+        a zstd decode session from now on"""
+        return self.L.qzSetSessionZstdDecodeRouteAMD(C.byref(self.s), self.ZSTDD_ROUTES.get(route, route))
 
     def set_crc32(self, polynomial, initial_value, reflect_in, reflect_out, xor_out):
         g = QzCrc32Config(polynomial, initial_value, reflect_in, reflect_out, xor_out)

@@ -20,6 +20,7 @@ def _sources():
     out.append(os.path.join(os.path.dirname(HERE), "include", "qzamd_zstd_dec.h"))
     out.append(os.path.join(os.path.dirname(HERE), "include", "qzamd_zstd_seq.h"))
     out.append(os.path.join(os.path.dirname(HERE), "include", "qzamd_zstd_parse.h"))
+    out.append(os.path.join(os.path.dirname(HERE), "include", "qzamd_zstd_blocks.h"))
     q = os.path.join(os.path.dirname(HERE), "include", "qatzip.h")
     if os.path.exists(q):
         out.append(q)

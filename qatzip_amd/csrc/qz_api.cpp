@@ -36,6 +36,7 @@
 #include "../../include/qzamd_zstd_dec.h"
 #include "../../include/qzamd_zstd_seq.h"
 #include "../../include/qzamd_zstd_parse.h"
+#include "../../include/qzamd_zstd_blocks.h"
 #include "qzd_zstdd_host.h"             /* a zstd frame's extent */
 #include "qz_frame.h"                   /* the F_* formats, bounds, the delivery rule, member framing, the crc folds */
 #include "qz_unframe.h"                 /* ... and of the decompress calls: member headers, sized members, frame plans, the crc folds */
@@ -49,6 +50,7 @@ struct Params {
     bool zstd_dec;                  /* ... made by qzSetupSessionZstdDecAMD: qzDecompress reads zstd frames */
     unsigned zstd_seq;              /* ... how its frames' sequences are coded: the flags of qzSetSessionZstdSeqAMD, 0 at setup */
     unsigned zstd_parse;            /* ... and how they are found: the depth of qzSetSessionZstdParseAMD, 0 at setup */
+    int zstdd_route;                /* a decode session's route (qzSetSessionZstdDecodeRouteAMD); -1 at setup: the context's */
 };
 
 struct Sess {
@@ -163,7 +165,7 @@ static int lz4s_to(Params &p, const QzSessionParamsLZ4S_T *s)
     if (s->lz4s_mini_match < 3 || s->lz4s_mini_match > 4) return QZ_PARAMS;
     p = g_def;
     from_common(p, s->common_params);
-    p.fmt = F_LZ4S; p.zstd = false; p.zstd_dec = false; p.zstd_seq = 0; p.zstd_parse = 0;
+    p.fmt = F_LZ4S; p.zstd = false; p.zstd_dec = false; p.zstd_seq = 0; p.zstd_parse = 0; p.zstdd_route = -1;
     p.cb = s->qzCallback; p.cb_ext = s->qzCallback_external; p.lz4s_mini_match = s->lz4s_mini_match;
     return check_common(p, true);
 }
@@ -381,6 +383,16 @@ extern "C" int qzSetSessionZstdParseAMD(QzSession_T *sess, unsigned int depth)
     if (!s || s->p.fmt != F_LZ4S || !s->p.zstd || (s->p.zstd_dec && s->p.direction != QZ_DIR_BOTH)) return QZ_PARAMS;
     if (depth > QZ_ZSTD_PARSE_DEPTH_MAX) return QZ_PARAMS;
     s->p.zstd_parse = depth;
+    return QZ_OK;
+}
+
+/* which frames a zstd decode session reads a block per lane group (include/qzamd_zstd_blocks.h); the next qzDecompress* call sees it */
+extern "C" int qzSetSessionZstdDecodeRouteAMD(QzSession_T *sess, int route)
+{
+    Sess *s = sess ? (Sess *)sess->internal : NULL;
+    if (!s || s->p.fmt != F_LZ4S || !s->p.zstd_dec) return QZ_PARAMS;
+    if (route < 0 || route > 2) return QZ_PARAMS;
+    s->p.zstdd_route = route;
     return QZ_OK;
 }
 
@@ -692,22 +704,28 @@ static int compress_lz4(QzSession_T *sess, Sess *s, const unsigned char *src, un
 
 /* LZ4 sessions and zstd decode sessions: the leading frames that fit (qz_frame_plan), a wave or more per frame in one launch.
  * extent / run / may_be_short are the codec: lz4_frame_extent, qzd_lz4_decompress_frames, QZ_SHORT_LAST, or
- * qzd_zd_frame_extent over zstd and skippable frames, qzd_zstd_decompress_frames, QZ_SHORT_LAST_UNSIZED */
+ * qzd_zd_frame_extent over zstd and skippable frames, qzd_zstd_decompress_frames, QZ_SHORT_LAST_UNSIZED.  With `walk`
+ * (qzd_zd_frame_walk) in place of extent and run, the plan's one walk also counts every frame's blocks and the zstd decoder
+ * gets them (qzd_zstd_decompress_frames_ex), so that a frame of many blocks takes the block route */
 typedef int (*FramesFn)(qzd_ctx *ctx, const uint8_t *d_comp, uint8_t *d_out, const void *h_segs, uint32_t nsegs, void *h_res);
 static int decompress_frames(QzSession_T *sess, Sess *s, const unsigned char *src, unsigned int *src_len, unsigned char *dest,
-                             unsigned int *dest_len, QzExtentFn extent, FramesFn run, QzShortRule may_be_short)
+                             unsigned int *dest_len, QzExtentFn extent, QzWalkFn walk, FramesFn run, QzShortRule may_be_short)
 {
     const uint32_t n = *src_len, cap = *dest_len;
     *src_len = 0; *dest_len = 0;
     s->out_resident = false;
     QzFramePlan pl;
-    int rc = qz_frame_plan(extent, src, n, cap, &pl);
+    int rc = qz_frame_plan_counted(extent, walk, src, n, cap, &pl);
     if (rc || pl.segs.empty()) return rc;
     rc = reserve(s, n, cap);
     if (rc) return rc;
     if (qzd_h2d(s->ctx, s->d_in, src, pl.ti) != QZD_OK) return QZ_FAIL;
     std::vector<qzd_lz4res> res(pl.segs.size());
-    if (run(s->ctx, s->d_in, s->d_out, pl.segs.data(), (uint32_t)pl.segs.size(), res.data()) != QZD_OK) return QZ_FAIL;
+    if (walk) {
+        if (s->p.zstdd_route >= 0) qzd_zstd_decode_route(s->ctx, s->p.zstdd_route);
+        if (qzd_zstd_decompress_frames_ex(s->ctx, s->d_in, s->d_out, pl.segs.data(), (uint32_t)pl.segs.size(), res.data(), pl.nblocks.data()) != QZD_OK) return QZ_FAIL;
+    }
+    else if (run(s->ctx, s->d_in, s->d_out, pl.segs.data(), (uint32_t)pl.segs.size(), res.data()) != QZD_OK) return QZ_FAIL;
     const int64_t produced = qz_frames_produced(pl.segs.data(), res.data(), pl.segs.size(), pl.alone, may_be_short);
     if (produced < 0) return QZ_FAIL;
     if (produced && qzd_d2h(s->ctx, dest, s->d_out, (uint64_t)produced) != QZD_OK) return QZ_FAIL;
@@ -981,9 +999,9 @@ static int decompress_direct(QzSession_T *sess, const unsigned char *src, unsign
         if (rc == QZ_OK || rc == QZ_BUF_ERROR) return rc;
         goto fail;
     }
-    if (s->p.fmt == F_LZ4) rc = decompress_frames(sess, s, src, src_len, dest, dest_len, lz4_frame_extent, qzd_lz4_decompress_frames, QZ_SHORT_LAST);
+    if (s->p.fmt == F_LZ4) rc = decompress_frames(sess, s, src, src_len, dest, dest_len, lz4_frame_extent, NULL, qzd_lz4_decompress_frames, QZ_SHORT_LAST);
     /* qzDecompress2 and the Crc64 calls (may_queue false) answer for a zstd decode session what they do for every LZ4s session */
-    else if (s->p.fmt == F_LZ4S && s->p.zstd_dec && may_queue) rc = decompress_frames(sess, s, src, src_len, dest, dest_len, qzd_zd_frame_extent, qzd_zstd_decompress_frames, QZ_SHORT_LAST_UNSIZED);
+    else if (s->p.fmt == F_LZ4S && s->p.zstd_dec && may_queue) rc = decompress_frames(sess, s, src, src_len, dest, dest_len, NULL, qzd_zd_frame_walk, NULL, QZ_SHORT_LAST_UNSIZED);
     else if (s->p.fmt == F_LZ4S) rc = QZ_UNSUPPORTED_FMT;
     else rc = decompress_deflate(sess, s, src, src_len, dest, dest_len, crc);
     sess->thd_sess_stat = rc;

@@ -114,24 +114,33 @@ static inline int64_t lz4_frame_extent(const uint8_t *p, uint64_t n, uint64_t *c
 /* The frame loop (src/qatzip_sw.c:555-571): the leading frames of src[0..n) whose content sizes fit cap one behind the other,
  * a segment each, and ti, the input they cover.  A frame without a content size gets the rest of cap, as far as its blocks can
  * reach, and ends the plan - sizes are unknown beyond it - as `alone`.  QZ_FAIL: the first frame is malformed or cut;
- * QZ_BUF_ERROR: it does not fit; a later such frame ends the plan, and the caller comes back with the rest. */
-struct QzFramePlan { std::vector<qzd_lz4seg> segs; uint32_t ti; bool alone; };
-static inline int qz_frame_plan(QzExtentFn extent, const unsigned char *src, uint32_t n, uint32_t cap, QzFramePlan *pl)
+ * QZ_BUF_ERROR: it does not fit; a later such frame ends the plan, and the caller comes back with the rest.
+ * With `walk` instead of `extent` (qzd_zd_frame_walk: the same walk, which also counts the frame's blocks) nblocks holds a
+ * count per segment, for the block route of the zstd decoder. */
+typedef int64_t (*QzWalkFn)(const uint8_t *p, uint64_t n, uint64_t *content, bool *has_content, uint64_t *bound, uint32_t *nblocks);
+struct QzFramePlan { std::vector<qzd_lz4seg> segs; uint32_t ti; bool alone; std::vector<uint32_t> nblocks; };
+static inline int qz_frame_plan_counted(QzExtentFn extent, QzWalkFn walk, const unsigned char *src, uint32_t n, uint32_t cap, QzFramePlan *pl)
 {
     uint64_t to = 0;
-    pl->segs.clear(); pl->ti = 0; pl->alone = false;
+    pl->segs.clear(); pl->ti = 0; pl->alone = false; pl->nblocks.clear();
     while (pl->ti < n && to < cap) {
         uint64_t content, bound; bool hc;
-        const int64_t ext = extent(src + pl->ti, n - pl->ti, &content, &hc, &bound);
+        uint32_t nb = 0;
+        const int64_t ext = walk ? walk(src + pl->ti, n - pl->ti, &content, &hc, &bound, &nb) : extent(src + pl->ti, n - pl->ti, &content, &hc, &bound);
         if (ext < 0) { if (pl->segs.empty()) return QZ_FAIL; break; }
         if (!hc) content = cap - to < bound ? cap - to : bound;
         if (to + content > cap) { if (pl->segs.empty()) return QZ_BUF_ERROR; break; }
         qzd_lz4seg g; g.in_off = pl->ti; g.out_off = to; g.in_len = (uint32_t)ext; g.out_cap = (uint32_t)content;
         pl->segs.push_back(g);
+        if (walk) pl->nblocks.push_back(nb);
         pl->ti += (uint32_t)ext; to += content;
         if (!hc) { pl->alone = true; break; }
     }
     return QZ_OK;
+}
+static inline int qz_frame_plan(QzExtentFn extent, const unsigned char *src, uint32_t n, uint32_t cap, QzFramePlan *pl)
+{
+    return qz_frame_plan_counted(extent, NULL, src, n, cap, pl);
 }
 
 /* Which segment of a plan may come out shorter than its out_cap.  Every other one has to fill it, or the next frame's output

@@ -256,6 +256,8 @@ static int ctx_create(int device, qzd_ctx **out, bool helper)
     if (hipMalloc(&c->d_running, 8) != hipSuccess || hipMalloc(&c->d_overflow, 4) != hipSuccess) QZD_CREATE_FAIL;
     /* QATZIP_AMD_LZ4D=auto|wave|blocks: how qzd_lz4_decompress_frames routes large frames (qzd_lz4_decode_route) */
     if (const char *e = getenv("QATZIP_AMD_LZ4D")) c->lz4d_route = !strcmp(e, "wave") ? 1 : !strcmp(e, "blocks") ? 2 : 0;
+    /* QATZIP_AMD_ZSTDD=auto|frame|blocks: which frames qzd_zstd_decompress_frames_ex reads a block per lane group (qzd_zstd_decode_route) */
+    if (const char *e = getenv("QATZIP_AMD_ZSTDD")) c->zstdd_route = !strcmp(e, "frame") ? 1 : !strcmp(e, "blocks") ? 2 : 0;
     hipHostMalloc((void **)&c->h_running, 8, hipHostMallocDefault);
     hipHostMalloc((void **)&c->h_overflow, 4, hipHostMallocDefault);
     /* watermark of a launch whose input is still arriving: read by the kernel over the link, so coherent + mapped */

@@ -62,6 +62,7 @@ struct qzd_ctx {
     uint8_t *d_lane; size_t lane_cap;               /* device-only scratch of the lane, wide, lazy and LZ4-HC compress paths (carve_symbols) */
     uint8_t *d_meta; size_t meta_cap;               /* device-only scratch of the block calls (qzd_meta.hip): slot streams, plan, ranges, hashes, CRCs */
     float inf_ms[4];
+    int zstdd_route;                /* qzd_zstd_decode_route: 0 auto, 1 a frame on its lanes, 2 a block per lane group wherever the count is known */
     int lz4d_route;                 /* qzd_lz4_decode_route: 0 auto, 1 a wave per frame, 2 a wave per block wherever a frame qualifies */
     bool no_stream_in;              /* this call is the batched retry of a launch that gave up waiting for its input */
     /* device arrays of the last two-phase inflate (phase A done, phase B still to run): two_phase() / two_phase_resolve() */

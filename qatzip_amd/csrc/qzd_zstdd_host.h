@@ -8,6 +8,7 @@
 #ifndef QZD_ZSTDD_HOST_H
 #define QZD_ZSTDD_HOST_H
 #include <stdint.h>
+#include <string.h>
 #ifndef __cplusplus
 #include <stdbool.h>
 #endif
@@ -117,6 +118,42 @@ static inline uint32_t qzd_zd_round(const qzk_zdseg *segs, uint32_t first, uint3
     *bytes = off + 16;
     return k;
 }
+#endif
+
+#ifdef QZK_ZSTDD_BLOCKS_H
+/* The block route (qzk_zstdd_blocks.h).  A frame whose block count the caller knows can have its blocks' bit streams read
+ * in parallel.  route: 0 auto - frames of QZD_ZD_BLOCKS_MIN blocks and more, the smallest count at which the route was not
+ * slower than stage E (profiles/zstd_decode_blocks.txt: 512 frames a call, 1.03 of stage E's time at one block a frame, 0.87
+ * at two, 0.50 at four) -, 1 no frame, 2 every frame whose count is known. */
+#define QZD_ZD_BLOCKS_MIN 2u
+static inline bool qzd_zdb_routed(int route, uint32_t nblocks)
+{
+    return route != 1 && nblocks != 0 && (route == 2 || nblocks >= QZD_ZD_BLOCKS_MIN);
+}
+/* The routed frames among the k frames of a round that starts at segment `first` (h_nblocks may be NULL: none).  fr[0 ..
+ * count) <- {segment of the round, hint, first descriptor}; *nblocks <- the round's descriptors, which lie behind the
+ * round's scratch (qzd_zd_round).  A block takes three bytes of input at least, so a hint above in_len / 3 is wrong
+ * whatever the frame holds: it is cut to in_len / 3 + 1, which is wrong too and keeps the descriptors within what the
+ * input could need.  Returns count. */
+static inline uint32_t qzd_zdb_round(const qzk_zdseg *segs, const uint32_t *h_nblocks, uint32_t first, uint32_t k, int route,
+                                     qzk_zdb_frame *fr, uint64_t *nblocks)
+{
+    uint32_t n = 0;
+    uint64_t nb = 0;
+    for (uint32_t i = 0; h_nblocks && i < k; i++) {
+        uint32_t hint = h_nblocks[first + i];
+        if (!qzd_zdb_routed(route, hint)) continue;
+        if (hint > segs[first + i].in_len / 3) hint = segs[first + i].in_len / 3 + 1;
+        qzk_zdb_frame f;
+        memset(&f, 0, sizeof f);
+        f.seg = i; f.hint = hint; f.first_blk = (uint32_t)nb;
+        fr[n++] = f;
+        nb += hint;
+    }
+    *nblocks = nb;
+    return n;
+}
+static inline uint64_t qzd_zdb_desc_bytes(uint64_t nblocks) { return nblocks * sizeof(qzk_zdb_desc) + 16; }
 #endif
 
 #endif
