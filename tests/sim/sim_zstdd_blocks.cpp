@@ -7,8 +7,10 @@
  * and the checksum kernel over all of them.
  * With SIM_ZSTDDB_MAIN the file is a program of its own: `sim_zstdd_blocks FILE...` decodes every file under route `blocks`
  * (the count from the host's walk; where the walk fails, a count of 1, 2 and 40) and under route `frame` and expects the
- * same answer of both, `sim_zstdd_blocks cut FILE` does so for the frame cut at every byte - each input in an allocation
- * of exactly its size, which is what a build with -fsanitize=address,undefined checks the loads against.
+ * same answer of both, `sim_zstdd_blocks cut FILE [FIRST LAST]` does so for the frame cut at every byte (at FIRST .. LAST
+ * bytes), `sim_zstdd_blocks recipe BASE RECIPES OUT_CAP frame|blocks` decodes BASE once per line `position value count` of
+ * RECIPES with that byte changed and that count, and prints `position value count status in_used out_len` - each input in
+ * an allocation of exactly its size, which is what a build with -fsanitize=address,undefined checks the loads against.
  */
 #define QZ_SIM 1
 #include "hipsim.h"
@@ -25,8 +27,11 @@ uint32_t sim_zstddb_desc_size(void) { return (uint32_t)sizeof(qzk_zdb_desc); }
 /* as sim_zstdd_frames (sim_zstdd.cpp), with nblocks (may be NULL) and route as qzd_zstd_decompress_frames_ex and
  * qzd_zstd_decode_route take them.  *routed <- the frames that took the block route; *launches <- the kernels launched.  The
  * descriptors lie behind the round's scratch, guard bytes behind them. */
-int sim_zstddb_frames(const uint8_t *comp, const void *segs_v, uint32_t nsegs, uint8_t *out, uint64_t out_size, void *res_v,
-                      const uint32_t *nblocks, int route, uint64_t scratch_cap, uint32_t *rounds, uint32_t *routed, uint32_t *launches)
+/* fail_blk (may be NULL): per segment the earliest block of a routed frame that Finish found refused, -1 where the frame is
+ * not routed, is accepted or is refused as a whole (its header, its count, its content size, its checksum) */
+int sim_zstddb_frames_fb(const uint8_t *comp, const void *segs_v, uint32_t nsegs, uint8_t *out, uint64_t out_size, void *res_v,
+                         const uint32_t *nblocks, int route, uint64_t scratch_cap, uint32_t *rounds, uint32_t *routed, uint32_t *launches,
+                         int32_t *fail_blk)
 {
     const qzk_zdseg *segs = (const qzk_zdseg *)segs_v;
     qzk_zdres *res = (qzk_zdres *)res_v;
@@ -36,6 +41,7 @@ int sim_zstddb_frames(const uint8_t *comp, const void *segs_v, uint32_t nsegs, u
     if (routed) *routed = 0;
     if (launches) *launches = 0;
     if (route == 1) nblocks = NULL;
+    for (uint32_t i = 0; fail_blk && i < nsegs; i++) fail_blk[i] = -1;
     std::vector<qzk_zdplan> plan(nsegs ? nsegs : 1);
     std::vector<qzk_zdb_frame> fr(nsegs ? nsegs : 1);
     int rc = 0;
@@ -61,6 +67,13 @@ int sim_zstddb_frames(const uint8_t *comp, const void *segs_v, uint32_t nsegs, u
             sim::launch(nb, 64, 0, [&] { qzk_zstdd_bfix_kernel(sg, plan.data(), fr.data(), nfr, nb, desc, sc); });
             sim::launch(nfr, 64, 0, [&] { qzk_zstdd_bfinish_kernel(sg, fr.data(), nfr, desc, rs); });
             nl += 5;
+            for (uint32_t j = 0; fail_blk && j < nfr; j++) {
+                const qzk_zdb_frame &f = fr[j];
+                for (uint32_t b = 0; !f.decided && b < f.nblk; b++) {
+                    const qzk_zdb_desc &d = desc[f.first_blk + b];
+                    if (d.herr || d.ferr || d.err) { fail_blk[first + f.seg] = (int32_t)b; break; }
+                }
+            }
         }
         sim::launch(k, 64, 0, [&] { qzk_zstdd_exec_kernel(out, sg, plan.data(), rs, k, sc); });
         sim::launch(k, 64, 0, [&] { qzk_zstdd_xxh_kernel(comp, out, sg, rs, k); });
@@ -79,6 +92,12 @@ int sim_zstddb_frames(const uint8_t *comp, const void *segs_v, uint32_t nsegs, u
         for (uint64_t b = 0; b < segs[i].out_cap && segs[i].out_off + b < out_size; b++) owned[segs[i].out_off + b] = 1;
     for (uint64_t b = 0; b < out_size; b++) if (!owned[b] && out[b] != 0xEE) rc = -3;
     return rc;
+}
+
+int sim_zstddb_frames(const uint8_t *comp, const void *segs_v, uint32_t nsegs, uint8_t *out, uint64_t out_size, void *res_v,
+                      const uint32_t *nblocks, int route, uint64_t scratch_cap, uint32_t *rounds, uint32_t *routed, uint32_t *launches)
+{
+    return sim_zstddb_frames_fb(comp, segs_v, nsegs, out, out_size, res_v, nblocks, route, scratch_cap, rounds, routed, launches, NULL);
 }
 
 /* qzd_zstd_count_blocks: the Plan walk without descriptors */
@@ -141,10 +160,33 @@ static int both(const char *name, const std::vector<uint8_t> &frame, size_t n, u
 }
 int main(int argc, char **argv)
 {
-    if (argc < 2) { fprintf(stderr, "usage: sim_zstdd_blocks [cut] FILE...\n"); return 2; }
+    if (argc < 2) { fprintf(stderr, "usage: sim_zstdd_blocks FILE... | cut FILE [FIRST LAST] | recipe BASE RECIPES OUT_CAP frame|blocks\n"); return 2; }
     const bool cut = !strcmp(argv[1], "cut");
     int fails = 0;
-    for (int a = cut ? 2 : 1; a < argc; a++) {
+    if (!strcmp(argv[1], "recipe")) {
+        if (argc != 6 || (strcmp(argv[5], "frame") && strcmp(argv[5], "blocks"))) { fprintf(stderr, "usage: sim_zstdd_blocks recipe BASE RECIPES OUT_CAP frame|blocks\n"); return 2; }
+        std::vector<uint8_t> frame = slurp(argv[2]);
+        const uint32_t cap = (uint32_t)strtoul(argv[4], NULL, 10);
+        const int route = !strcmp(argv[5], "frame") ? 1 : 2;
+        FILE *f = fopen(argv[3], "r");
+        if (!f) { fprintf(stderr, "cannot open %s\n", argv[3]); return 2; }
+        unsigned long pos, value, count;
+        while (fscanf(f, "%lu %lu %lu", &pos, &value, &count) == 3) {
+            if (pos >= frame.size() || value > 255) { fprintf(stderr, "%s: byte %lu = %lu is outside the frame\n", argv[3], pos, value); fails++; continue; }
+            const uint8_t keep = frame[pos];
+            frame[pos] = (uint8_t)value;
+            qzk_zdres r;
+            const int rc = decode_prefix(frame, frame.size(), cap, (uint32_t)count, route, &r, NULL);
+            frame[pos] = keep;
+            if (rc) { fprintf(stderr, "%s byte %lu = %lu, count %lu: guard %d\n", argv[2], pos, value, count, rc); fails++; }
+            printf("%lu %lu %lu %d %u %u\n", pos, value, count, r.status, r.in_used, r.out_len);
+        }
+        fclose(f);
+        printf("sim_zstdd_blocks: %d failures\n", fails);
+        return fails ? 1 : 0;
+    }
+    if (cut && argc != 3 && argc != 5) { fprintf(stderr, "usage: sim_zstdd_blocks cut FILE [FIRST LAST]\n"); return 2; }
+    for (int a = cut ? 2 : 1; a < (cut ? 3 : argc); a++) {
         const std::vector<uint8_t> frame = slurp(argv[a]);
         uint64_t content = 0, bound = 0; bool hc = false;
         const int64_t ext = qzd_zd_frame_extent(frame.data(), frame.size(), &content, &hc, &bound);
@@ -152,7 +194,11 @@ int main(int argc, char **argv)
         if (ext > 0) cap = (uint32_t)(hc ? content : bound);
         if (cap > (1u << 20)) cap = 1u << 20;
         if (!cut) fails += both(argv[a], frame, frame.size(), cap);
-        else for (size_t n = 0; n <= frame.size(); n++) fails += both(argv[a], frame, n, cap);
+        else {
+            size_t lo = 0, hi = frame.size();
+            if (argc == 5) { lo = strtoul(argv[3], NULL, 10); hi = strtoul(argv[4], NULL, 10); if (hi > frame.size()) hi = frame.size(); }
+            for (size_t n = lo; n <= hi; n++) fails += both(argv[a], frame, n, cap);
+        }
     }
     printf("sim_zstdd_blocks: %d failures\n", fails);
     return fails ? 1 : 0;

@@ -250,5 +250,27 @@ def test_under_sanitizers(tmp_path, idx):
     assert len(files) >= 25
     r = subprocess.run([exe] + files, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "0 failures" in r.stdout, r.stdout + r.stderr
-    r = subprocess.run([exe, "cut", os.path.join(B.GOLDEN, "h_repeat_each.zst")], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "0 failures" in r.stdout, r.stdout + r.stderr
+    # (h_70_blocks: more groups than one wave of 64 lanes takes; s_between_repeat: its first 4 KiB of cuts)
+    for cut in (["h_repeat_each.zst"], ["h_70_blocks.zst"], ["s_between_repeat.zst", "0", str(CUT_MAX)]):
+        r = subprocess.run([exe, "cut", os.path.join(B.GOLDEN, cut[0])] + cut[1:], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0 and "0 failures" in r.stdout, r.stdout + r.stderr
+
+
+CUT_MAX = 4096
+
+
+def test_a_frame_cut_at_every_byte_under_both_routes(idx):
+    """what the program above compares in C, here: the frame cut at every byte gives the same {status, in_used, out_len} and
+    bytes under route `blocks` - the host walk's count, and where the walk fails the whole frame's - and under route `frame`"""
+    for name in ("h_repeat_each", "h_70_blocks", "s_between_repeat"):
+        e = next(c for c in idx["cases"] if c["name"] == name)
+        fr = B.frame_bytes(e)
+        last = min(len(fr), CUT_MAX)
+        for first in range(0, last + 1, 512):                            # (calls of 512 cuts: every cut has the frame's out_cap)
+            cuts = [fr[:n] for n in range(first, min(first + 512, last + 1))]
+            caps = [e["cap"]] * len(cuts)
+            ra, oa = D.decode_frames(cuts, caps)
+            assert all(r == (D.ETRUNC, 0, 0) if len(c) < len(fr) else r == tuple(e["sim"]) for c, r in zip(cuts, ra)), name
+            for counts in (None, [e["nblocks"]] * len(cuts)):
+                rb, ob = B.decode_frames(cuts, caps, nblocks=counts)
+                assert [first + n for n, (a, b) in enumerate(zip(ra, rb)) if a != b] == [] and oa == ob, name

@@ -39,8 +39,8 @@ def _load():
     if _S is None:
         S = C.CDLL(build_so())
         u32p = C.POINTER(C.c_uint32)
-        S.sim_zstddb_frames.argtypes = [C.c_char_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int,
-                                        C.c_uint64, u32p, u32p, u32p]
+        S.sim_zstddb_frames_fb.argtypes = [C.c_char_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int,
+                                           C.c_uint64, u32p, u32p, u32p, C.c_void_p]
         S.sim_zstddb_count.argtypes = [C.c_char_p, C.c_void_p, C.c_uint32, C.c_void_p]
         S.sim_zstddb_count.restype = None
         for f in (S.sim_zstddb_group, S.sim_zstddb_min, S.sim_zstddb_desc_size):
@@ -58,7 +58,8 @@ def blocks_min():
 
 
 def decode(comp, segs, out_size, nblocks=None, route="blocks", scratch_cap=0):
-    """-> (guard rc, results, the output image, {rounds, routed, launches})"""
+    """-> (guard rc, results, the output image, {rounds, routed, launches, fail_blk: per segment the earliest refused block of
+    a routed frame, -1 where there is none})"""
     S = _load()
     segs = np.ascontiguousarray(segs, dtype=D.SEG)
     res = np.zeros(max(len(segs), 1), dtype=D.RES)
@@ -66,9 +67,11 @@ def decode(comp, segs, out_size, nblocks=None, route="blocks", scratch_cap=0):
     nb = None if nblocks is None else np.ascontiguousarray(nblocks, dtype=np.uint32)
     assert nb is None or len(nb) == len(segs)
     rounds, routed, launches = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
-    rc = S.sim_zstddb_frames(bytes(comp), segs.ctypes.data, len(segs), out, out_size, res.ctypes.data, None if nb is None else nb.ctypes.data,
-                             ROUTES[route], scratch_cap, C.byref(rounds), C.byref(routed), C.byref(launches))
-    return rc, res[:len(segs)], out.raw[:out_size], {"rounds": rounds.value, "routed": routed.value, "launches": launches.value}
+    fail = np.zeros(max(len(segs), 1), dtype=np.int32)
+    rc = S.sim_zstddb_frames_fb(bytes(comp), segs.ctypes.data, len(segs), out, out_size, res.ctypes.data, None if nb is None else nb.ctypes.data,
+                                ROUTES[route], scratch_cap, C.byref(rounds), C.byref(routed), C.byref(launches), fail.ctypes.data)
+    return rc, res[:len(segs)], out.raw[:out_size], {"rounds": rounds.value, "routed": routed.value, "launches": launches.value,
+                                                     "fail_blk": [int(x) for x in fail[:len(segs)]]}
 
 
 def decode_frames(frames, caps, nblocks=None, route="blocks", gap=0, scratch_cap=0, info=None):
